@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """BlinDNO FNO-NIO training throughput on MI355X (BASELINE.json config C).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 Workload (one "step"): NIOFP2D_FNO(2,3,100,25,3,12,32,2) train step on a 128x128 grid,
@@ -11,10 +11,16 @@ ranks (N>1), fused Adam (lr 5e-4).  Synthetic standardised bags live in HBM (eac
 owns its shard of a 4096-bag set).  value = world * B * K / max-over-ranks(time of K steps)
 snapshot-bags/s.
 
-Extra fields: "roofline" for the dominant kernel (algorithmic bytes or flops per launch /
-average launch time, measured with HIP events on the launch stream during the timed
-region) and "cpu_baseline" (the float32 CPU oracle timed on this host on a bounded
-sample of the same workload, rank 0 at N=1 only).
+A plain run sets up, warms up, times the K steps and prints the result line.  --dump-outputs DIR
+also writes what the last timed step computed (its output field, loss, flat gradient and the
+parameters after its Adam update) as DIR/<name>.npy; the inputs are seeded, so two builds run
+with the same arguments can be compared array by array.
+
+--full adds the legs that take runs of their own after the timed region: "roofline" for the
+dominant kernel (algorithmic bytes or flops per launch / average launch time, measured with
+HIP events on the launch stream), "roofline_spectral", "parity" (the benched step against the
+reference's fp32 CPU step and an fp64 arbiter) and "cpu_baseline" (the float32 CPU oracle
+timed on this host on a bounded sample of the same workload, rank 0 at N=1 only).
 """
 from __future__ import annotations
 
@@ -97,7 +103,7 @@ def build_model(cfg_name, N, dev):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=30, help="timed steps")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--serial-heads", action="store_true", help="run the two heads on one stream")
     ap.add_argument("--forked-heads", action="store_true",
@@ -108,10 +114,16 @@ def parse():
     ap.add_argument("--grid", type=int, default=None)
     ap.add_argument("--T", type=int, default=None)
     ap.add_argument("--bags", type=int, default=4096, help="dataset size (all ranks)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="cpu baseline budget")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the GPU-vs-CPU-reference parity leg")
-    ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: dominant-kernel and spectral "
+                         "rooflines, the parity leg and the CPU baseline (each can be switched off below)")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="cpu baseline budget (--full)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="with --full: skip the GPU-vs-CPU-reference parity leg")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="with --full: skip the rooflines")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP graphs")
     ap.add_argument("--overlap", default="auto", choices=("auto", "on", "off"),
                     help="two-graph step with the heads' gradient all-reduce beside the encoder's "
@@ -120,8 +132,31 @@ def parse():
                     help="channel-mix operand precision of the 2D spectral layers (default: fp16 "
                          "for config E as BASELINE.json names it, fp32 otherwise)")
     ap.add_argument("--timer-steps", type=int, default=4,
-                    help="eager steps after the timed region that time the dominant kernel (graph mode)")
-    return ap.parse_args()
+                    help="eager steps after the timed region that time the dominant kernel (graph mode, "
+                         "--full)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Write each tensor of ``arrays`` as path/<name>.npy in float32, at most DUMP_BUDGET_BYTES in
+    all: an array over its equal share of the budget is cut to a fixed sample of its flattened
+    elements (sorted indices drawn without replacement from RandomState(0), the same at every run
+    of the same shapes)."""
+    os.makedirs(path, exist_ok=True)
+    fits = 4 * sum(t.numel() for t in arrays.values()) <= DUMP_BUDGET_BYTES
+    share = DUMP_BUDGET_BYTES // (4 * max(1, len(arrays)))
+    for name, t in arrays.items():
+        t = t.detach().to(torch.float32)
+        if not fits and t.numel() > share:
+            pick = np.sort(np.random.RandomState(0).choice(t.numel(), share, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(pick).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def main():
@@ -200,6 +235,7 @@ def main():
     hostp = {"batch_select": 0.0, "draw": 0.0, "step": 0.0, "n": 0}
 
     n_loss = [0]             # steps whose loss went into loss_acc (the kernel-timer steps do not)
+    last = {}                # the latest step's output field and loss (--dump-outputs)
 
     def step(i, eager=False, count_loss=True):
         t0_ = time.perf_counter()
@@ -210,7 +246,8 @@ def main():
             t1_ = time.perf_counter()
             idx = (draw_distinct if a.config == "C_attn" else blindno.draw_bag)(T)[1]
             t2_ = time.perf_counter()
-            graphed.step(idx)
+            key = graphed.step(idx)
+            last.update(out=graphed.out[key], loss=graphed.loss[key])
             n_loss[0] += 1
             t3_ = time.perf_counter()
             hostp["batch_select"] += t1_ - t0_
@@ -223,6 +260,7 @@ def main():
         loss.backward()
         dp.step()
         opt.zero_grad()
+        last.update(out=out.detach(), loss=loss.detach())
         if count_loss:
             loss_acc.add_(loss.detach())
             n_loss[0] += 1
@@ -234,7 +272,7 @@ def main():
         if rank == 0:
             print(f"[bench] warmup step {i}: {time.perf_counter() - tw:.3f}s", file=sys.stderr, flush=True)
     timer = None
-    if not a.no_kernel_timer:
+    if a.full and not a.no_kernel_timer:
         # the dominant kernel: the bag-level projection (configs with the fused snapshot encoder);
         # config D: its snapshot CNN's implicit-GEMM convolutions as one family
         timer = timing.KernelTimer("blindno_conv2d" if a.config == "D" else timing.DOMINANT)
@@ -262,6 +300,11 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # what the last timed step left: copies taken before any later leg steps or replays again
+        dumped = {"out": last["out"].clone(), "loss": last["loss"].clone(), "grad": opt.grad.clone(),
+                  "params": opt.flat.clone()}
     if timer and graphed is not None:
         # graph replays cannot be hooked: time the dominant kernel (the identical launches) with
         # HIP events on its stream over a few eager steps right after the timed region
@@ -370,7 +413,7 @@ def main():
                     res["roofline"]["valu_issue_util_benched_step_source"] = sb.get("source")
             if a.config in ("C", "E"):
                 res["roofline_spectral"] = spectral_roofline(model, grid, B, T, N, dev, pmc_prefix=pre)
-        if world == 1 and a.config in ("A", "B", "C", "D", "E"):
+        if a.full and world == 1 and a.config in ("A", "B", "C", "D", "E"):
             # the reference's CPU path on the same weights / inputs: accuracy parity of the
             # benched step (the "rel-L2 drift error" half of BASELINE's metric), then its timing
             if not a.no_parity:
@@ -384,6 +427,8 @@ def main():
             for k, v in (getattr(graphed, "host_times", None) or {}).items():
                 hb["step." + k] = round(1e6 * v / hostp["n"], 1)
             res["host_us_per_step"] = hb
+        if dumped is not None:
+            dump_outputs(a.dump_outputs, dumped)
         print(json.dumps(res))
     if world > 1:
         dist.destroy_process_group()

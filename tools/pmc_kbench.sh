@@ -2,11 +2,11 @@
 # PMC passes over tools/kbench.py (filter $2) -- one counter group per rocprofv3 run.
 TAG=${1:-x}; FILT=${2:-project}
 export TMPDIR=/tmp
-mkdir -p gpurun_out/pmck_$TAG
+OUT=${OUT:-out}; mkdir -p $OUT/pmck_$TAG
 i=0
 for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_VALU_TRANS_F32 SQ_THREAD_CYCLES_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY" "SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAVES" "GRBM_GUI_ACTIVE GRBM_COUNT" "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
-  timeout -s KILL 120 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d gpurun_out/pmck_$TAG/p$i -o run \
-    -- python3 tools/kbench.py "$FILT" > gpurun_out/pmck_$TAG/p$i.log 2>&1
+  timeout -s KILL 120 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $OUT/pmck_$TAG/p$i -o run \
+    -- python3 tools/kbench.py "$FILT" > $OUT/pmck_$TAG/p$i.log 2>&1
   rc=$?; echo "pass $i rc=$rc"; [ $rc -eq 0 ] || exit $rc
 done

@@ -810,6 +810,73 @@ int blindno_tok_attn_bwd(const float* dY, const float* X, const float* lw, const
                          float* dX, float* dlw, float* dlb, float* scratch, int B, int L,
                          int64_t D, blindno_stream_t stream);
 
+/* --- 3D Fourier layer (SpectralConv3d / FNO3d, 2d_FPE/FNOModules.py:245-366) ----------------
+ * The padded field x[n][c][x][y][z] (Bn, C, P1, P2, P3) is the 2D field x[n][c][h][w] with
+ * h = x P2 + y (P1 P2 rows) and w = z: the last-axis transforms, the 1x1 Conv3d epilogue and its
+ * weight gradient are blindno_rowdft, blindno_rowidft_epi / _bwd and blindno_conv_wgrad called
+ * with (P1 := P1 P2, P2 := P3, m2 := m3).  Kept frequencies per axis as stated at the top for
+ * rows: K1 = min(2 m1, P1) along x, K2 = min(2 m2, P2) along y, kept index j = jx K2 + jy.
+ *   rowspec At[n][k3][c][x P2 + y]     spectrum Xs[n][k3][c][jx K2 + jy]
+ *   rowcoef Z[n][x P2 + y][k3][c]      wpack Wt[k3][jx K2 + jy][ci][co]
+ * Limits: C <= 32, m1 <= P1, m2 <= P2, m3 <= min(48, P3/2 + 1), P1 K2 <= 8192, and the row
+ * kernels' 32-bit sizes on the flattened view; blindno_spectral3d_ok returns 1 inside them. */
+int blindno_spectral3d_ok(int Bn, int Ci, int Co, int P1, int P2, int P3, int m1, int m2, int m3);
+
+/* The transforms over y and x around the channel mix (the middle of rfftn -> compl_mul3d on the
+ * four corners -> irfftn, 2d_FPE/FNOModules.py:273-287), complex GEMMs on the f32 matrix cores:
+ * y first (the plane shrinks to P1 x K2), then x; the mix; the x and y inverses.
+ * Tx (P1, K1), Ty (P2, K2) complex: T[p][j] = e^{-2 pi i r_j p / P} (blindno.ops.twiddle_axis).
+ * Wt: blindno_pack_w3d's (carries c_k3 / (P1 P2 P3)).  Y: scratch (Bn, m3, C_out, K1 K2) complex.
+ * dir 0 (forward): Xs = DFT_xy(At) (Bn, m3, Ci, K1 K2) saved for the weight gradient;
+ *                  Z = IDFT_xy(sum_i Xs Wt)                      (Co channels).
+ * dir 1 (adjoint): At holds the row DFT of the output gradient (Co channels);
+ *                  Xs = DFT_xy(At) = the gradient of the mixed spectrum (Bn, m3, Co, K1 K2);
+ *                  Z = IDFT_xy(sum_o conj(Wt) Xs)                (Ci channels).
+ * Z is Z[n][h][k3][c], or in the A-tile order when blindno_spectrum_tile_layout(Bn, C_out,
+ * P1 P2, P3, m3) is 1 (what the row inverse of that shape reads).  With Xs of both directions,
+ * blindno_mix_wgrad(Xs0, Xs1, dWt, ..., K1 := K1 K2, m2 := m3) is the gradient of Wt. */
+int blindno_colpass3d(const float* At, const float* Wt, float* Xs, float* Y, float* Z,
+                      const float* Tx, const float* Ty, int Bn, int Ci, int Co, int P1, int P2,
+                      int P3, int m1, int m2, int m3, int dir, blindno_stream_t stream);
+
+/* Pack weights1..4 (Ci, Co, m1, m2, m3) cfloat (2d_FPE/FNOModules.py:260-263) into Wt, scaled by
+ * c_k3 / (P1 P2 P3) (c = 1 at k3 = 0 and at the Nyquist bin of an even P3, else 2).  A frequency
+ * inside several corners (2 m1 > P1 or 2 m2 > P2) takes the last one, as the reference's slice
+ * assignments in the order 1, 2, 3, 4 do (:277-284).  Unpack: the gradients of weights1..4 from
+ * dWt (same scale); an entry that lost an overlap gets exactly 0. */
+int blindno_pack_w3d(const float* w1, const float* w2, const float* w3, const float* w4, float* Wt,
+                     int Ci, int Co, int m1, int m2, int m3, int P1, int P2, int P3,
+                     blindno_stream_t stream);
+int blindno_unpack_w3d(const float* dWt, float* dw1, float* dw2, float* dw3, float* dw4, int Ci,
+                       int Co, int m1, int m2, int m3, int P1, int P2, int P3,
+                       blindno_stream_t stream);
+
+/* fc0 + permute + F.pad on the right of three axes (2d_FPE/FNOModules.py:336-339):
+ * in (Bn, N1, N2, N3, Cin) channels-last -> x0 (Bn, C, P1, P2, P3), zero outside the grid.
+ * C, Cin <= 32.  Backward: optional d_in (may be NULL) and per-chunk partial sums of dW0 (C*Cin)
+ * then db0 (C) into partial[nchunk][C*Cin + C], nchunk = blindno_lift3d_bwd_nchunk(...). */
+int blindno_lift3d_fwd(const float* in, const float* w0, const float* b0, float* x0, int Bn,
+                       int N1, int N2, int N3, int Cin, int C, int P1, int P2, int P3,
+                       blindno_stream_t stream);
+int blindno_lift3d_bwd_nchunk(int Bn, int N1, int N2, int N3);
+int blindno_lift3d_bwd(const float* dx0, const float* in, const float* w0, float* d_in,
+                       float* partial, int nchunk, int Bn, int N1, int N2, int N3, int Cin, int C,
+                       int P1, int P2, int P3, blindno_stream_t stream);
+
+/* crop + permute + fc1 + GELU + fc2 (2d_FPE/FNOModules.py:360-364): z (Bn, C, P1, P2, P3) ->
+ * out (Bn, N1, N2, N3, Cout) on the crop x < N1, y < N2, z < N3.  Hd <= 128, Cout <= 8, C <= 32.
+ * Backward: dz (Bn, C, P1, P2, P3), written whole (exactly 0 on the padding), and per-chunk
+ * partials [dW1 (Hd*C) | db1 (Hd) | dW2 (Cout*Hd) | db2 (Cout)] into partial[nchunk][...],
+ * nchunk = blindno_project3d_bwd_nchunk(...); the hidden layer is recomputed, never stored. */
+int blindno_project3d_fwd(const float* z, const float* w1, const float* b1, const float* w2,
+                          const float* b2, float* out, int Bn, int C, int P1, int P2, int P3,
+                          int N1, int N2, int N3, int Hd, int Cout, blindno_stream_t stream);
+int blindno_project3d_bwd_nchunk(int Bn, int N1, int N2, int N3);
+int blindno_project3d_bwd(const float* z, const float* w1, const float* b1, const float* w2,
+                          const float* dout, float* dz, float* partial, int nchunk, int Bn, int C,
+                          int P1, int P2, int P3, int N1, int N2, int N3, int Hd, int Cout,
+                          blindno_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

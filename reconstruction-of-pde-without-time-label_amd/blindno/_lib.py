@@ -164,6 +164,17 @@ SIGNATURES = {
     "blindno_deeponet_bag_nblk": "i",
     "blindno_deeponet_bag_fwd": "pppppp" + "iiii" + "f" + "s",
     "blindno_deeponet_bag_bwd": "pppppppp" + "iiiii" + "f" + "s",
+    # 3D Fourier layer (csrc/spectral3d.hip)
+    "blindno_spectral3d_ok": "iiiiiiiii",
+    "blindno_colpass3d": "ppppppp" + "iiiiiiiiii" + "s",
+    "blindno_pack_w3d": "ppppp" + "iiiiiiii" + "s",
+    "blindno_unpack_w3d": "ppppp" + "iiiiiiii" + "s",
+    "blindno_lift3d_fwd": "pppp" + "iiiiiiiii" + "s",
+    "blindno_lift3d_bwd_nchunk": "iiii",
+    "blindno_lift3d_bwd": "ppppp" + "i" + "iiiiiiiii" + "s",
+    "blindno_project3d_fwd": "pppppp" + "iiiiiiiiii" + "s",
+    "blindno_project3d_bwd_nchunk": "iiii",
+    "blindno_project3d_bwd": "ppppppp" + "i" + "iiiiiiiiii" + "s",
 }
 
 # entry points returning int64_t (byte counts) instead of an error code / int count

@@ -17,9 +17,10 @@ encoder kernels and the 1D GPE head layout:
 The attention UNet ("BlinDNO") maps to blindno.unet: PermInvUNet_attn (2d_FPE),
 its ConvBlock copy PermInvUNet_attn_NC (2d_Non_conservative_FPE), PermInvUNet_attn1D(_bag)
 (1d_FPE) and the one-head 1d_GPE copies.  Classes outside the hot-path scope (Transolver /
-plain-UNet / 3D / ODE variants) are importable -- the
+plain-UNet / NIOFP3D / ODE variants) are importable -- the
 reference scripts import them next to the in-scope ones -- but raise NotImplementedError when
-constructed.
+constructed.  ``FNOModules`` is whole: SpectralConv3d / FNO3d run on the HIP device like the 1D
+and 2D classes (blindno.ops.FNO3dFn); only NIOFP3D, which needs Encoder3D, stays out.
 """
 from __future__ import annotations
 

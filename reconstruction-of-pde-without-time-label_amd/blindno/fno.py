@@ -146,8 +146,8 @@ class FNO2d(nn.Module):
 
 
 class SpectralConv3d(nn.Module):
-    """Layout-compatible placeholder for the 3D layer (2d_FPE/FNOModules.py:245-288).
-    3D is outside this build's scope (no reference script uses it): forward raises."""
+    """2d_FPE/FNOModules.py:245-288: rfftn -> compl_mul3d on the four corner blocks (weights1..4
+    assigned in that order, so a later one wins where corners overlap) -> irfftn."""
 
     def __init__(self, in_channels, out_channels, modes1, modes2, modes3):
         super().__init__()
@@ -159,11 +159,13 @@ class SpectralConv3d(nn.Module):
             setattr(self, f"weights{k}", nn.Parameter(self.scale * torch.rand(*shp, dtype=torch.cfloat)))
 
     def forward(self, x):
-        raise NotImplementedError("SpectralConv3d/FNO3d are outside the blindno hot-path scope")
+        return ops.SpectralConv3dFn.apply(x, self.weights1, self.weights2, self.weights3, self.weights4)
 
 
 class FNO3d(nn.Module):
-    """Layout-compatible placeholder (2d_FPE/FNOModules.py:290-366); forward raises."""
+    """2d_FPE/FNOModules.py:290-366: fc0, right pad by 2 on three axes, four Fourier layers
+    (``n_layers`` is ignored, as in the reference; GELU after the first three), crop, fc1 -> GELU
+    -> fc2 = Linear(128, output_dim).  ``device`` is accepted and unused, as in the reference."""
 
     def __init__(self, modes, width, n_layers, input_dim, output_dim, device="cpu"):
         super().__init__()
@@ -179,4 +181,9 @@ class FNO3d(nn.Module):
         self.fc2 = nn.Linear(128, output_dim)
 
     def forward(self, x):
-        raise NotImplementedError("SpectralConv3d/FNO3d are outside the blindno hot-path scope")
+        ps = [self.fc0.weight, self.fc0.bias]
+        for k in range(ops.FNO3D_LAYERS):
+            s, c = getattr(self, f"conv{k}"), getattr(self, f"w{k}")
+            ps += [s.weights1, s.weights2, s.weights3, s.weights4, c.weight, c.bias]
+        ps += [self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias]
+        return ops.FNO3dFn.apply(self.padding, x, *ps)

@@ -945,6 +945,256 @@ class FNOFn(torch.autograd.Function):
         return (None, d_inp, *grads)
 
 
+# ---------------------------------------------------------------------------- 3D Fourier layer
+# SpectralConv3d / FNO3d (2d_FPE/FNOModules.py:245-366).  The padded field (Bn, C, P1, P2, P3) is
+# the 2D field (Bn, C, R = P1 P2, P3): the last-axis DFT, the row inverse with its 1x1-conv
+# epilogue / adjoint and the conv weight gradient are the 2D row kernels on that view; the
+# transforms over y and x around the mix are blindno_colpass3d (csrc/spectral3d.hip).
+
+_TW3 = {}
+
+
+def twiddle_axis(P: int, m: int, device) -> torch.Tensor:
+    """T[p][j] = e^{-2 pi i r_j p / P} at the kept frequencies r_j of one axis (kept_rows), as
+    (P, K, 2) fp32 built in double (include/blindno.h blindno_colpass3d's Tx / Ty)."""
+    dev = torch.device(device)
+    key = (P, m, dev.index)
+    t = _TW3.get(key)
+    if t is None:
+        r = torch.tensor(kept_rows(m, P), dtype=torch.int64)
+        p = torch.arange(P, dtype=torch.int64)
+        ph = ((p[:, None] * r[None, :]) % P).to(torch.float64) * (2.0 * torch.pi / P)
+        t = torch.stack([torch.cos(ph), -torch.sin(ph)], -1).to(F32).to(dev).contiguous()
+        _TW3[key] = t
+    return t
+
+
+class Spec3Shape:
+    """Geometry of one 3D spectral layer over a padded field; rejects what the reference rejects
+    (a corner slice longer than its axis) and what the kernels cannot take."""
+
+    def __init__(self, Bn, Ci, Co, P1, P2, P3, m1, m2, m3):
+        self.Bn, self.Ci, self.Co = Bn, Ci, Co
+        self.P1, self.P2, self.P3, self.m1, self.m2, self.m3 = P1, P2, P3, m1, m2, m3
+        if m1 > P1 or m2 > P2:
+            raise BlindnoError(f"modes ({m1}, {m2}) exceed the grid ({P1}, {P2})")
+        if m3 > P3 // 2 + 1:
+            raise BlindnoError(f"modes3 {m3} exceed P3//2+1 = {P3 // 2 + 1}")
+        if not query("blindno_spectral3d_ok", Bn, Ci, Co, P1, P2, P3, m1, m2, m3):
+            raise BlindnoError(
+                f"3D spectral layer (Bn {Bn}, C {Ci}->{Co}, grid {P1}x{P2}x{P3}, modes {m1},{m2},{m3}) "
+                "is past the kernels' limits (include/blindno.h blindno_spectral3d_ok)")
+        self.R = P1 * P2
+        self.K1, self.K2 = kept_rows_count(m1, P1), kept_rows_count(m2, P2)
+        self.KK = self.K1 * self.K2
+
+
+def k_colpass3d(At, Wt, sh: Spec3Shape, direction):
+    """DFT over y then x at the kept frequencies + mix + the two inverses.  Returns (saved
+    spectrum (Bn, m3, Cin, K1 K2), row coefficients Z (Bn, R, m3, Cout))."""
+    cin, cout = (sh.Ci, sh.Co) if direction == 0 else (sh.Co, sh.Ci)
+    Xs = _empty(sh.Bn, sh.m3, cin, sh.KK, 2, like=At)
+    Y = _empty(sh.Bn, sh.m3, cout, sh.KK, 2, like=At)
+    Z = _empty(sh.Bn, sh.R, sh.m3, cout, 2, like=At)
+    call("blindno_colpass3d", ptr(At), ptr(Wt), ptr(Xs), ptr(Y), ptr(Z),
+         ptr(twiddle_axis(sh.P1, sh.m1, At.device)), ptr(twiddle_axis(sh.P2, sh.m2, At.device)),
+         sh.Bn, sh.Ci, sh.Co, sh.P1, sh.P2, sh.P3, sh.m1, sh.m2, sh.m3, direction, stream_ptr())
+    return Xs, Z
+
+
+def k_pack_w3d(ws, sh: Spec3Shape):
+    """weights1..4 (Ci, Co, m1, m2, m3) cfloat -> Wt (m3, K1 K2, Ci, Co, 2)."""
+    Wt = torch.empty(sh.m3, sh.KK, sh.Ci, sh.Co, 2, dtype=F32, device=ws[0].device)
+    call("blindno_pack_w3d", *[ptr(w) for w in ws], ptr(Wt), sh.Ci, sh.Co, sh.m1, sh.m2, sh.m3,
+         sh.P1, sh.P2, sh.P3, stream_ptr())
+    return Wt
+
+
+def k_unpack_w3d(dWt, ws, sh: Spec3Shape):
+    dws = [torch.empty_like(w) for w in ws]
+    call("blindno_unpack_w3d", ptr(dWt), *[ptr(d) for d in dws], sh.Ci, sh.Co, sh.m1, sh.m2,
+         sh.m3, sh.P1, sh.P2, sh.P3, stream_ptr())
+    return dws
+
+
+def _check_w3d(ws, Ci):
+    w = ws[0]
+    if w.dim() != 5 or not w.is_complex() or w.shape[0] != Ci or any(v.shape != w.shape for v in ws):
+        raise BlindnoError("SpectralConv3d weights must be four cfloat (Ci, Co, m1, m2, m3) tensors")
+
+
+def spec3_forward(x, act, Wt, sh: Spec3Shape):
+    At = k_rowdft(x, sh.Bn, sh.Ci, sh.R, sh.P3, sh.m3, act)
+    return k_colpass3d(At, Wt, sh, 0)
+
+
+def spec3_backward(dz, X, Wt, sh: Spec3Shape):
+    """Adjoint of spec3_forward: (dWt, GZ) for the layer's output gradient dz."""
+    At = k_rowdft(dz, sh.Bn, sh.Co, sh.R, sh.P3, sh.m3, 0)
+    G, GZ = k_colpass3d(At, Wt, sh, 1)
+    return k_mix_wgrad(X, G, sh.Bn, sh.Ci, sh.Co, sh.KK, sh.m3), GZ
+
+
+class SpectralConv3dFn(torch.autograd.Function):
+    """Bare SpectralConv3d: x (Bn, Ci, P1, P2, P3) -> (Bn, Co, P1, P2, P3)."""
+
+    @staticmethod
+    def forward(ctx, x, *ws):
+        if x.dim() != 5 or len(ws) != 4:
+            raise BlindnoError("SpectralConv3d takes a (Bn, Ci, P1, P2, P3) field and four weights")
+        Bn, Ci, P1, P2, P3 = x.shape
+        _check_w3d(ws, Ci)
+        Co, m1, m2, m3 = ws[0].shape[1:]
+        sh = Spec3Shape(Bn, Ci, Co, P1, P2, P3, m1, m2, m3)
+        require_device(x, *ws)
+        x = _c(x)
+        ws = [_c(w) for w in ws]
+        Wt = k_pack_w3d(ws, sh)
+        X, Z = spec3_forward(x, 0, Wt, sh)
+        y = k_rowidft_epi(Z, None, None, None, Bn, Co, sh.R, P3, m3, 0)
+        ctx.sh = sh
+        ctx.save_for_backward(X, Wt, *ws)
+        return y.view(Bn, Co, P1, P2, P3)
+
+    @staticmethod
+    def backward(ctx, gy):
+        X, Wt, *ws = ctx.saved_tensors
+        sh = ctx.sh
+        dWt, GZ = spec3_backward(_c(gy), X, Wt, sh)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx, _, _ = k_rowidft_bwd(GZ, None, None, None, sh.Bn, sh.Ci, sh.R, sh.P3, sh.m3, 0)
+            dx = dx.view(sh.Bn, sh.Ci, sh.P1, sh.P2, sh.P3)
+        return (dx, *k_unpack_w3d(dWt, ws, sh))
+
+
+FNO3D_LAYERS = 4   # the reference's FNO3d has four Fourier layers whatever n_layers says (:322-329)
+
+
+def _fno3d_geometry(inp, padding):
+    if inp.dim() != 5:
+        raise BlindnoError("FNO3d takes a channels-last (Bn, N1, N2, N3, Cin) input")
+    Bn, N1, N2, N3, Cin = inp.shape
+    if min(Bn, N1, N2, N3, Cin) < 1 or padding < 1:
+        raise BlindnoError("FNO3d: empty input, or no padding to crop (x[..., :-pad])")
+    return Bn, N1, N2, N3, Cin, N1 + padding, N2 + padding, N3 + padding
+
+
+def lift3d(inp, w0, b0, P):
+    """fc0 + permute + right pad to P = (P1, P2, P3): (Bn, N1, N2, N3, Cin) -> (Bn, C, P1, P2, P3)."""
+    Bn, N1, N2, N3, Cin = inp.shape
+    C = w0.shape[0]
+    x0 = _empty(Bn, C, *P, like=inp)
+    call("blindno_lift3d_fwd", ptr(inp), ptr(w0), ptr(b0), ptr(x0), Bn, N1, N2, N3, Cin, C, *P,
+         stream_ptr())
+    return x0
+
+
+def lift3d_backward(dx0, inp, w0, P, need_inp_grad=True):
+    """(d_in or None, dW0, db0) of lift3d."""
+    Bn, N1, N2, N3, Cin = inp.shape
+    C = w0.shape[0]
+    nchunk = query("blindno_lift3d_bwd_nchunk", Bn, N1, N2, N3)
+    partial = _empty(nchunk, C * Cin + C, like=inp)
+    d_inp = torch.empty_like(inp) if need_inp_grad else None
+    call("blindno_lift3d_bwd", ptr(dx0), ptr(inp), ptr(w0), ptr(d_inp), ptr(partial), nchunk, Bn,
+         N1, N2, N3, Cin, C, *P, stream_ptr())
+    g = reduce_partials(partial, nchunk, C * Cin + C)
+    return d_inp, g[:C * Cin].view(C, Cin), g[C * Cin:]
+
+
+def project3d(z, fc1w, fc1b, fc2w, fc2b, N):
+    """crop to N = (N1, N2, N3) + fc1 + GELU + fc2: (Bn, C, P1, P2, P3) -> (Bn, N1, N2, N3, Cout)."""
+    Bn, C, P1, P2, P3 = z.shape
+    Hd, Cout = fc1w.shape[0], fc2w.shape[0]
+    out = _empty(Bn, *N, Cout, like=z)
+    call("blindno_project3d_fwd", ptr(z), ptr(fc1w), ptr(fc1b), ptr(fc2w), ptr(fc2b), ptr(out), Bn,
+         C, P1, P2, P3, *N, Hd, Cout, stream_ptr())
+    return out
+
+
+def project3d_backward(z, fc1w, fc1b, fc2w, gout, N):
+    """(dz (zero on the padding), dW1, db1, dW2, db2) of project3d."""
+    Bn, C, P1, P2, P3 = z.shape
+    Hd, Cout = fc1w.shape[0], fc2w.shape[0]
+    np_p = Hd * C + Hd + Cout * Hd + Cout
+    nchunk = query("blindno_project3d_bwd_nchunk", Bn, *N)
+    partial = _empty(nchunk, np_p, like=z)
+    dz = _empty(Bn, C, P1, P2, P3, like=z)
+    call("blindno_project3d_bwd", ptr(z), ptr(fc1w), ptr(fc1b), ptr(fc2w), ptr(gout), ptr(dz),
+         ptr(partial), nchunk, Bn, C, P1, P2, P3, *N, Hd, Cout, stream_ptr())
+    gp = reduce_partials(partial, nchunk, np_p)
+    o1, o2, o3 = Hd * C, Hd * C + Hd, Hd * C + Hd + Cout * Hd
+    return dz, gp[:o1].view(Hd, C), gp[o1:o2], gp[o2:o3].view(Cout, Hd), gp[o3:]
+
+
+class FNO3dFn(torch.autograd.Function):
+    """Whole FNO3d forward (2d_FPE/FNOModules.py:334-366) as one autograd node.
+    prm = [fc0w, fc0b, (weights1..4, cw, cb) * 4, fc1w, fc1b, fc2w, fc2b]."""
+
+    @staticmethod
+    def forward(ctx, padding, inp, *prm):
+        Bn, N1, N2, N3, Cin, P1, P2, P3 = _fno3d_geometry(inp, padding)
+        n = FNO3D_LAYERS
+        if len(prm) != 2 + 6 * n + 4:
+            raise BlindnoError("FNO3d: bad parameter list")
+        C = prm[0].shape[0]
+        _check_w3d(prm[2:6], C)
+        m1, m2, m3 = prm[2].shape[2:]
+        sh = Spec3Shape(Bn, C, C, P1, P2, P3, m1, m2, m3)
+        require_device(inp, *prm)
+        inp = _c(inp)
+        prm = [_c(p) for p in prm]
+        x0 = lift3d(inp, prm[0], prm[1], (P1, P2, P3))
+        src, act = x0, 0
+        Xs, Wts, zs = [], [], []
+        for k in range(n):
+            off = 2 + 6 * k
+            cw, cb = prm[off + 4], prm[off + 5]
+            Wt = k_pack_w3d(prm[off:off + 4], sh)
+            X, Z = spec3_forward(src, act, Wt, sh)
+            z = k_rowidft_epi(Z, src, cw, cb, Bn, C, sh.R, P3, m3, act)
+            Xs.append(X)
+            Wts.append(Wt)
+            zs.append(z)
+            src, act = z, 1
+        fc1w, fc1b, fc2w, fc2b = prm[2 + 6 * n:]
+        out = project3d(zs[-1].view(Bn, C, P1, P2, P3), fc1w, fc1b, fc2w, fc2b, (N1, N2, N3))
+        ctx.sh, ctx.n = sh, n
+        ctx.save_for_backward(inp, x0, *Xs, *Wts, *zs, *prm)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        sh, n = ctx.sh, ctx.n
+        t = ctx.saved_tensors
+        inp, x0 = t[0], t[1]
+        Xs, Wts, zs = t[2:2 + n], t[2 + n:2 + 2 * n], t[2 + 2 * n:2 + 3 * n]
+        prm = t[2 + 3 * n:]
+        Bn, C, P = sh.Bn, sh.Ci, (sh.P1, sh.P2, sh.P3)
+        grads: List[Optional[torch.Tensor]] = [None] * len(prm)
+        o = 2 + 6 * n
+        dz, grads[o], grads[o + 1], grads[o + 2], grads[o + 3] = project3d_backward(
+            zs[-1].view(Bn, C, *P), prm[o], prm[o + 1], prm[o + 2], _c(gout), tuple(inp.shape[1:4]))
+        for k in reversed(range(n)):
+            off = 2 + 6 * k
+            ws, cw = prm[off:off + 4], prm[off + 4]
+            src, act = (x0, 0) if k == 0 else (zs[k - 1], 1)
+            dWt, GZ = spec3_backward(dz, Xs[k], Wts[k], sh)
+            grads[off:off + 4] = k_unpack_w3d(dWt, ws, sh)
+            if C <= 4:
+                dz_new, gw, gb = k_rowidft_bwd(GZ, dz, cw, src, Bn, C, sh.R, sh.P3, sh.m3, act, True)
+            else:
+                gw, gb = k_conv_wgrad(dz, src, Bn, C, sh.R, sh.P3, act)
+                dz_new, _, _ = k_rowidft_bwd(GZ, dz, cw, src, Bn, C, sh.R, sh.P3, sh.m3, act)
+            grads[off + 4] = gw.view_as(cw)
+            grads[off + 5] = gb
+            dz = dz_new
+        d_inp, grads[0], grads[1] = lift3d_backward(dz, inp, prm[0], P, ctx.needs_input_grad[1])
+        grads = [g if ctx.needs_input_grad[2 + i] else None for i, g in enumerate(grads)]
+        return (None, d_inp, *grads)
+
+
 # ---------------------------------------------------------------------------- grouped heads
 # Two FNO2d heads on the same input run as ONE chain of launches over 2 B samples: every
 # kernel selects the weights of the sample's head (blindno_*_g entry points): head g's copy of a

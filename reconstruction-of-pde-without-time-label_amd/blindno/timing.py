@@ -98,6 +98,16 @@ def cost(name, args):
         flops = 2 * N * Co * Ho * Wo * K
         nbytes = 4 * (N * Ci * Hi * Wi + N * Co * Ho * Wo + Co * K)
         return nbytes, flops
+    if name == "blindno_colpass3d":
+        Bn, Ci, Co, P1, P2, P3, m1, m2, m3, d = (_i(args, k) for k in range(7, 17))
+        cin, cout = (Ci, Co) if d == 0 else (Co, Ci)
+        K1, K2 = min(2 * m1, P1), min(2 * m2, P2)
+        # read At, write Z and the saved spectrum, read Wt; the mixed spectrum Y stays a scratch
+        # the math does not need in HBM.  One complex FMA = 8 flops: y then x transform per input
+        # channel, the mix, x then y inverse per output channel
+        nbytes = 8 * (Bn * m3 * (cin + cout) * P1 * P2 + Bn * m3 * cin * K1 * K2 + m3 * K1 * K2 * Ci * Co)
+        flops = 8 * Bn * m3 * ((cin + cout) * (P1 * P2 * K2 + P1 * K2 * K1) + K1 * K2 * Ci * Co)
+        return nbytes, flops
     if name == "blindno_conv_wgrad":
         nchunk, Bn, C, P1, P2 = (_i(args, k) for k in range(3, 8))
         pts = Bn * P1 * P2

@@ -388,7 +388,10 @@ int blindno_reduce_partials_pieces(const void* const* partials, void* const* out
 /* ... where a whole segment i with upks[i] = u >= 0 is a packed spectral weight gradient
  * (m2, 2 m1, Ci, Co) complex stored unpacked into the weights1 / weights2 gradient layouts
  * ud[2 u], ud[2 u + 1] with ushp[4 u ..] = (Ci, Co, m1, m2) (the unpack folded into the
- * reduction; at most 8 per launch of 48 segments). */
+ * reduction; at most 8 per launch of 48 segments: a group of 48 consecutive segments that
+ * holds more is an error).  blindno_reduce_segs_limit(0) is that group size, (1) the number of
+ * folded unpacks a group may hold. */
+int blindno_reduce_segs_limit(int what);
 int blindno_reduce_partials_pieces_u(const void* const* partials, void* const* outs,
                                      const int* nchunks, const int* nps, const int* e0s,
                                      const int* e1s, const int* upks, void* const* ud,
@@ -524,8 +527,11 @@ int blindno_gather_flat(const void* const* srcs, const int64_t* offs, const int6
 int blindno_gather_batch(const void* const* srcs, void* const* dsts, const int64_t* rows,
                          const int64_t* nsrc, int nseg, const int64_t* ids, int B,
                          blindno_stream_t stream);
-int blindno_adam(float* p, const float* g, float* m, float* v, int64_t n, float beta1,
-                 float beta2, float eps, float step_size, float bc2s, float gscale,
+/* One torch.optim.Adam step (no weight decay, no amsgrad) on flat buffers, g scaled by gscale:
+ * step_size = lr / (1 - beta1^t), bc2s = sqrt(1 - beta2^t).  beta1, beta2 are doubles so that
+ * 1 - beta is rounded to fp32 once, as torch does (ABI version 3; they were floats before). */
+int blindno_adam(float* p, const float* g, float* m, float* v, int64_t n, double beta1,
+                 double beta2, float eps, float step_size, float bc2s, float gscale,
                  blindno_stream_t stream);
 
 /* --- density evaluators (fp64) ----------------------------------------------------------- */

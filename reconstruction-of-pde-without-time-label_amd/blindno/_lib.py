@@ -69,7 +69,7 @@ SIGNATURES = {
     "blindno_mse_finish_acc": "pilpps",
     "blindno_mse_fwd": "ppplipppps",
     "blindno_rowsq": "pppiiiiiis",
-    "blindno_adam": "pppplffffffs",
+    "blindno_adam": "pppplddffffs",
     "blindno_gpe_solve": "ppppddiiipppiiis",
     "blindno_trapz_rows": "ppppiis",
     # size queries (return a count, not an error code)
@@ -112,6 +112,7 @@ SIGNATURES = {
     "blindno_reduce_partials_multi": "ppppis",
     "blindno_reduce_partials_pieces": "ppppppis",
     "blindno_reduce_partials_pieces_u": "pppppppppis",
+    "blindno_reduce_segs_limit": "i",
     "blindno_finish_multi": "pppppppppippppis",
     "blindno_unpack_w2d_multi": "ppppis",
     "blindno_pack_w2d_multi": "ppppis",

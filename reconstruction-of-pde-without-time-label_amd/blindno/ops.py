@@ -298,14 +298,34 @@ class _Deferred:
                 done.append(p)
         return done
 
+    @staticmethod
+    def _segment_count(r):
+        """Segments flush emits for the recorded reduction ``r``: its redirected pieces and the
+        gaps between them (one when nothing is redirected, folded or not)."""
+        n, pos = 0, 0
+        for e0, e1, _ in sorted(r[4], key=lambda t: t[0]):
+            n += 2 if e0 > pos else 1
+            pos = e1
+        return n + (1 if pos < r[3] else 0)
+
     def _fold_unpacks(self):
         """Match each recorded unpack to the kernel that finishes its dWt -- a mix job with no
         sample split (all its weight groups unpacked) or a whole reduction -- so that kernel
-        stores dWt unpacked (W2dUnpack, csrc/wgrad.h) and the unpack launch goes.  Returns
+        stores dWt unpacked (W2dUnpack, csrc/wgrad.h) and the unpack launch goes; reductions only
+        up to the segment table's limit per launch group (blindno_reduce_segs_limit).  Returns
         ({mix job: {group: (dw1, dw2)}}, {reduction: (dw1, dw2, (Ci, Co, m1, m2))}, the
         unpacks left for blindno_unpack_w2d_multi)."""
         mixu, redu, rest = {}, {}, []
         taken = {}
+        # a launch group of the reductions (blindno_reduce_segs_limit(0) consecutive segments of
+        # flush's list) stores at most blindno_reduce_segs_limit(1) of them unpacked; the unpacks
+        # past that stay with the unpack launch.  Folding does not change a reduction's segment
+        # count, so its group is known here.
+        gsegs, gmax = query("blindno_reduce_segs_limit", 0), query("blindno_reduce_segs_limit", 1)
+        seg0, folded, pos = [], {}, 0
+        for r in self.red:
+            seg0.append(pos)
+            pos += self._segment_count(r)
         for u in self.unp:
             dW, d1, d2, (Ci, Co, m1, m2, P1), _ = u
             hit = False
@@ -325,8 +345,11 @@ class _Deferred:
                     for ri, r in enumerate(self.red):
                         if (r[1].data_ptr() == p and r[3] == dW.numel() and not r[4] and ri not in redu
                                 and r[3] == 4 * Ci * Co * m1 * m2):
-                            redu[ri] = (d1, d2, (Ci, Co, m1, m2))
-                            hit = True
+                            grp = seg0[ri] // gsegs
+                            if folded.get(grp, 0) < gmax:
+                                folded[grp] = folded.get(grp, 0) + 1
+                                redu[ri] = (d1, d2, (Ci, Co, m1, m2))
+                                hit = True
                             break
             if not hit:
                 rest.append(u)

@@ -922,14 +922,14 @@ __global__ __launch_bounds__(kBlock) void rowsq_kernel(const float* __restrict__
 __global__ __launch_bounds__(kBlock) void adam_kernel(float* __restrict__ p,
                                                       const float* __restrict__ g,
                                                       float* __restrict__ m, float* __restrict__ v,
-                                                      int64_t n, float beta1, float beta2,
-                                                      float eps, float step_size, float bc2s,
-                                                      float gscale) {
+                                                      int64_t n, float beta1, float omb1,
+                                                      float beta2, float omb2, float eps,
+                                                      float step_size, float bc2s, float gscale) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     const float gi = g[i] * gscale;
-    const float mi = fmaf(1.0f - beta1, gi - m[i], m[i]);   // exp_avg.lerp_(grad, 1-beta1)
-    const float vi = fmaf((1.0f - beta2) * gi, gi, v[i] * beta2);
+    const float mi = fmaf(omb1, gi - m[i], m[i]);           // exp_avg.lerp_(grad, 1-beta1)
+    const float vi = fmaf(omb2 * gi, gi, v[i] * beta2);
     m[i] = mi;
     v[i] = vi;
     const float denom = sqrtf(vi) / bc2s + eps;
@@ -940,7 +940,7 @@ __global__ __launch_bounds__(kBlock) void adam_kernel(float* __restrict__ p,
 }  // namespace
 
 // ------------------------------------------------------------------------------ C ABI
-BLINDNO_API int blindno_abi_version(void) { return 2; }
+BLINDNO_API int blindno_abi_version(void) { return 3; }
 
 BLINDNO_API const char* blindno_error_string(int code) {
   return hipGetErrorString((hipError_t)code);
@@ -1236,6 +1236,13 @@ static int reduce_segs_build(const void* const* partials, void* const* outs, con
   }
   segs.cum[k] = blocks;
   return 0;
+}
+
+// The segment table's limits, for the host code that decides which unpacks to fold
+// (blindno.ops._Deferred._fold_unpacks): what = 0: segments per launch group (kRedSegs),
+// 1: folded unpacks per launch group (kRedUnpack).
+BLINDNO_API int blindno_reduce_segs_limit(int what) {
+  return what == 0 ? kRedSegs : (what == 1 ? kRedUnpack : 0);
 }
 
 BLINDNO_API int blindno_reduce_partials_pieces_u(const void* const* partials, void* const* outs,
@@ -1615,10 +1622,13 @@ BLINDNO_API int blindno_gather_batch(const void* const* srcs, void* const* dsts,
   return (int)hipGetLastError();
 }
 
-BLINDNO_API int blindno_adam(float* p, const float* g, float* m, float* v, int64_t n, float beta1,
-                             float beta2, float eps, float step_size, float bc2s, float gscale,
-                             void* stream) {
+// beta1, beta2 in double: 1 - beta is formed in double and rounded once, as torch.optim.Adam's
+// lerp weight and addcmul value are (1.0f - 0.999f is 1.3e-5 off 0.001f, and v with it)
+BLINDNO_API int blindno_adam(float* p, const float* g, float* m, float* v, int64_t n,
+                             double beta1, double beta2, float eps, float step_size, float bc2s,
+                             float gscale, void* stream) {
   adam_kernel<<<grid_for(n, kBlock, 16384), kBlock, 0, (hipStream_t)stream>>>(
-      p, g, m, v, n, beta1, beta2, eps, step_size, bc2s, gscale);
+      p, g, m, v, n, (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps,
+      step_size, bc2s, gscale);
   return (int)hipGetLastError();
 }

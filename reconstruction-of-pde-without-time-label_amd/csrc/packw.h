@@ -78,10 +78,12 @@ __device__ __forceinline__ void w2d_transpose_tile(const PackSegs& segs, int b, 
 
 // segments -> block table for w2d_transpose_tile; false if a segment has overlapping kept rows
 // (the element-wise kernels handle those)
+// (decided before any cum[] is written: the caller's element-wise table stays as it built it)
 inline bool w2d_tiled_segs(PackSegs& segs, int64_t& blocks) {
   blocks = 0;
-  for (int i = 0; i < segs.nseg; ++i) {
+  for (int i = 0; i < segs.nseg; ++i)
     if (2 * segs.m1[i] >= segs.P1[i]) return false;
+  for (int i = 0; i < segs.nseg; ++i) {
     segs.cum[i] = (int)blocks;
     const int64_t nio = (segs.Ci[i] * segs.Co[i] + 31) / 32, nk = (segs.m2[i] + 31) / 32;
     blocks += 2 * (int64_t)segs.m1[i] * nio * nk;

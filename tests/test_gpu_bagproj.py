@@ -1,7 +1,8 @@
 """The bag-level projection entry point (csrc/bagproj.hip, blindno_project_bag_fwd) called through
 the C ABI against a float64 torch restatement of what it replaces: the FNO_input projection
 (crop -> fc1 -> GELU -> fc2, 2d_FPE/FNOModules.py:234-239) of every snapshot of a bag and the
-weighted bag mean over the snapshots (2d_FPE/NIOModules.py:569-575).
+weighted bag mean over the snapshots (2d_FPE/NIOModules.py:569-575).  The statistics it leaves are
+then fed to blindno_project_bag_bwd, whose fc1 / fc2 gradients are compared with float64 autograd.
 
 The shapes reach the workgroup set-up's edge cases: one snapshot per bag, a bag size that is not
 a multiple of the 8-snapshot chunk, more snapshots than the 256 threads that stage the bag
@@ -62,3 +63,29 @@ def test_project_bag_fwd_matches_fp64(B, U, C, P, N):
     # fp32 fc1 / fc2 and the A&S erf (|err| <= 4.2e-7) against float64 (measured <= 2e-7)
     assert e_u <= 2e-6
     assert e_v <= 2e-6
+
+    # the backward entry point on the statistics just produced: the fc1 / fc2 gradients, reduced
+    # from the per-workgroup partials [dW1 (Hd C) | db1 (Hd) | dW2 (Hd) | db2], against float64
+    # autograd of the same restatement (dz = NULL: its consumers form it on load)
+    from blindno import ops
+    ghat = torch.randn(B, N * N, device=dev, generator=g)
+    nchunk = query("blindno_project_bag_bwd_nchunk", B, N, N)
+    np_ = 128 * C + 2 * 128 + 1
+    partial = torch.full((nchunk, np_), float("nan"), device=dev)
+    call("blindno_project_bag_bwd", ptr(stats), ptr(ghat), ptr(w2), ptr(lw), None, None, ptr(partial),
+         nchunk, B, U, C, P, P, N, N, 128, stream_ptr())
+    gp = ops.reduce_partials(partial, nchunk, np_)
+    torch.cuda.synchronize()
+    leaves = [t.double().cpu().requires_grad_(True) for t in (w1, b1, w2, b2)]
+    w1d, b1d, w2d, b2d = leaves
+    pr = _gelu(zc.cpu() @ w1d.t() + b1d) @ w2d.t() + b2d
+    ub = (lw.double().cpu().view(1, U, 1) * pr[..., 0]).sum(1)
+    (ub * ghat.double().cpu()).sum().backward()
+    gp = gp.double().cpu()
+    got = (gp[:128 * C].view(128, C), gp[128 * C:128 * C + 128], gp[128 * C + 128:128 * C + 256].view(1, 128),
+           gp[128 * C + 256:])
+    assert torch.isfinite(gp).all()
+    for name, a, leaf in zip(("dw1", "db1", "dw2", "db2"), got, leaves):
+        e = _rel(a, leaf.grad)
+        print(f"B={B} U={U} C={C} N={N}: {name} {e:.2e}")
+        assert e <= 2e-6, (name, e)

@@ -194,6 +194,7 @@ WGRAD_CASES = [
     (4, 64, 32, 16, 128, 3, 3, 2, 2, 1, 1),    # 576 + 1: a ragged last column tile
     (6, 1, 32, 32, 64, 1, 7, 1, 2, 0, 3),      # 7 + 1, 64 x 64 tiles
     (3, 5, 13, 11, 7, 3, 2, 3, 2, 2, 1),       # odd output plane: the scalar loaders, bias as a column
+    (3, 32, 16, 16, 200, 3, 3, 1, 1, 1, 1),    # Co = 200: several row tiles, the last one ragged (mg < M)
 ]
 
 

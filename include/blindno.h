@@ -883,8 +883,13 @@ int blindno_project3d_bwd(const float* z, const float* w1, const float* b1, cons
                           int P1, int P2, int P3, int N1, int N2, int N3, int Hd, int Cout,
                           blindno_stream_t stream);
 
+/* The NIOFP3D snapshot encoder's 3D convolutions (blindno_conv3d_*, csrc/conv3d.hip) are part of
+ * this ABI and are declared in their own header, included at the end of this file. */
+
 #ifdef __cplusplus
 }
 #endif
+
+#include "blindno_conv3d.h"
 
 #endif /* BLINDNO_H */

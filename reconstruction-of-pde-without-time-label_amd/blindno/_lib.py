@@ -178,6 +178,18 @@ SIGNATURES = {
     "blindno_project3d_bwd": "ppppppp" + "i" + "iiiiiiiiii" + "s",
 }
 
+# One table per header: SIGNATURES binds what include/blindno.h itself declares, this one what
+# include/blindno_conv3d.h declares (the NIOFP3D encoder convolutions, csrc/conv3d.hip;
+# geometry = 15 ints).  load() types both, call() / query() reach both.
+SIGNATURES_CONV3D = {
+    "blindno_conv3d_fwd_nsplit": "i" * 15,
+    "blindno_conv3d_fwd": "ppppp" + "i" + "i" * 15 + "s",
+    "blindno_conv3d_bwd_data_nsplit": "i" * 15,
+    "blindno_conv3d_bwd_data": "pppp" + "i" + "i" * 15 + "s",
+    "blindno_conv3d_wgrad_nsplit": "i" * 15,
+    "blindno_conv3d_bwd_weight": "pppp" + "i" + "i" * 15 + "s",
+}
+
 # entry points returning int64_t (byte counts) instead of an error code / int count
 RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))}
 
@@ -204,7 +216,7 @@ def load():
                 "`python reconstruction-of-pde-without-time-label_amd/build.py` "
                 "(there is no CPU fallback)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in SIGNATURES.items():
+        for name, sig in {**SIGNATURES, **SIGNATURES_CONV3D}.items():
             fn = getattr(lib, name)
             fn.argtypes = [_CT[c] for c in sig]
             fn.restype = ctypes.c_int64 if name in RET64 else ctypes.c_int
@@ -215,7 +227,7 @@ def load():
 
 
 def exported_symbols():
-    return list(SIGNATURES) + ["blindno_error_string"]
+    return list(SIGNATURES) + list(SIGNATURES_CONV3D) + ["blindno_error_string"]
 
 
 def stream_ptr(device=None):

@@ -17,10 +17,12 @@ encoder kernels and the 1D GPE head layout:
 The attention UNet ("BlinDNO") maps to blindno.unet: PermInvUNet_attn (2d_FPE),
 its ConvBlock copy PermInvUNet_attn_NC (2d_Non_conservative_FPE), PermInvUNet_attn1D(_bag)
 (1d_FPE) and the one-head 1d_GPE copies.  Classes outside the hot-path scope (Transolver /
-plain-UNet / NIOFP3D / ODE variants) are importable -- the
+plain-UNet / ODE variants) are importable -- the
 reference scripts import them next to the in-scope ones -- but raise NotImplementedError when
 constructed.  ``FNOModules`` is whole: SpectralConv3d / FNO3d run on the HIP device like the 1D
-and 2D classes (blindno.ops.FNO3dFn); only NIOFP3D, which needs Encoder3D, stays out.
+and 2D classes (blindno.ops.FNO3dFn).  NIOFP3D (defined by the two 2D experiments' NIOModules,
+2d_FPE/NIOModules.py:720-788) is served by blindno.nio.NIOFP3D, and every ``Baselines`` has
+ConvBlock3D / Encoder3D / Encoder3D_down (blindno.ops.Conv3dFn, csrc/conv3d.hip).
 """
 from __future__ import annotations
 
@@ -115,7 +117,9 @@ _COMMON_DON = dict(FFN=_don.FFN, DeepOnetNoBiasOrg=_don.DeepOnetNoBiasOrg,
                    FeedForwardNN=_don.FeedForwardNN, FourierFeatures=_don.FourierFeatures,
                    Swish=_don.Swish, Sin=_don.Sin, activation=_don.activation,
                    kaiming_init=_don.kaiming_init, init_xavier=_don.init_xavier)
-_COMMON_BASE = dict(ConvBlock=_enc.ConvBlock, Encoder2D=_enc.Encoder2D, Encoder=_enc.Encoder)
+_COMMON_BASE = dict(ConvBlock=_enc.ConvBlock, Encoder2D=_enc.Encoder2D, Encoder=_enc.Encoder,
+                    ConvBlock3D=_enc.ConvBlock3D, Encoder3D=_enc.Encoder3D,
+                    Encoder3D_down=_enc.Encoder3D_down)
 
 
 def _oos(where, *names):
@@ -123,19 +127,19 @@ def _oos(where, *names):
 
 
 _2D_OOS = ("NIOFP2D_Trans", "NIOFP2D_Trans_attn", "NIOFP2D_attn",
-           "NIOFP_ode", "NIOFP3D", "PermInvUNet")
+           "NIOFP_ode", "PermInvUNet")
 
 EXPERIMENTS = {
     "2d_FPE": dict(
         NIOModules=dict(NIOFP2D=_NIOFP2D_2d, NIOFP2D_FNO=_NIOFP2D_FNO_2d, NIOFP=_NIOFP_1d,
-                        NIOFP2D_FNO_attn=_NIOFP2D_FNO_attn_2d,
+                        NIOFP2D_FNO_attn=_NIOFP2D_FNO_attn_2d, NIOFP3D=_nio.NIOFP3D,
                         PermInvUNet_attn=_unet.PermInvUNet_attn, ConvNeXtBlock=_unet.ConvNeXtBlock,
                         TemporalSelfAttention=_unet.TemporalSelfAttention,
                         draw_bag=_nio.draw_bag, **_oos("2d_FPE/NIOModules.py", *_2D_OOS)),
     ),
     "2d_Non_conservative_FPE": dict(
         NIOModules=dict(NIOFP2D=_NIOFP2D_nc, NIOFP2D_FNO=_NIOFP2D_FNO_nc, NIOFP=_NIOFP_1d,
-                        NIOFP2D_FNO_attn=_NIOFP2D_FNO_attn_nc,
+                        NIOFP2D_FNO_attn=_NIOFP2D_FNO_attn_nc, NIOFP3D=_nio.NIOFP3D,
                         PermInvUNet_attn=_unet.PermInvUNet_attn_NC,
                         TemporalSelfAttention=_unet.TemporalSelfAttention,
                         draw_bag=_nio.draw_bag,

@@ -1,9 +1,10 @@
 """Snapshot-bag (time-label-free) models: NIOFP2D_FNO, NIOFP_FNO, NIOFP2D, NIOFP,
-NIOFP_schrodinger -- drop-in for the reference's NIOModules.
+NIOFP_schrodinger, NIOFP3D -- drop-in for the reference's NIOModules.
 
 Same constructor signatures, attribute names and initialisation order as
 2d_FPE/NIOModules.py:14-83,508-581, 2d_Non_conservative_FPE/NIOModules.py:13-82,503-577,
-1d_FPE/NIOModules.py:15-155 and 1d_GPE/NIOModules.py:160-289.
+1d_FPE/NIOModules.py:15-155, 1d_GPE/NIOModules.py:160-289 and (NIOFP3D)
+2d_FPE/NIOModules.py:720-788.
 
 Train mode draws the bag exactly like the reference -- ``L = np.random.randint(50, T)``,
 ``idx = np.random.choice(T, L)`` (with replacement) from numpy's global RNG -- so a
@@ -19,8 +20,8 @@ import torch.nn as nn
 
 from . import ops
 from .deeponet import FFN, DeepOnetNoBiasOrg
-from .encoders import Encoder, Encoder2D
-from .fno import FNO1d, FNO2d, fno_params
+from .encoders import Encoder, Encoder2D, Encoder3D, Encoder3D_down
+from .fno import FNO1d, FNO2d, FNO3d, fno_params
 
 
 def draw_bag(T: int):
@@ -348,6 +349,44 @@ class NIOFP2D(nn.Module):
         ubar = ops.DeepONetBagFn.apply(w, basis, self.deeponet.b0)
         h = _bag_mean_2d(self, ubar.view(B, 1, nx * ny), grid, B, 1, nx, ny)
         return _run_heads(self, h)          # the two FNO heads as one grouped launch chain
+
+
+class NIOFP3D(nn.Module):
+    """3D NIO (DeepONet branch/trunk + one FNO3d), 2d_FPE/NIOModules.py:720-788 and
+    2d_Non_conservative_FPE/NIOModules.py:716-784.  ``down`` selects Encoder3D_down (depth <= 32)
+    instead of Encoder3D (33 <= depth <= 64)."""
+
+    def __init__(self, input_dimensions_trunk, n_hidden_layers, neurons, n_basis, fno_layers,
+                 width, modes, output_dim, device, down=False):
+        super().__init__()
+        output_dimensions = n_basis
+        self.trunk = FFN(input_dimensions_trunk, output_dimensions, n_hidden_layers, neurons,
+                         "leaky_relu", 0.0)
+        self.fno_layers = fno_layers
+        self.branch = (Encoder3D_down if down else Encoder3D)(output_dimensions)
+        self.deeponet = DeepOnetNoBiasOrg(self.branch, self.trunk)
+        self.fc0 = nn.Linear(4, width)
+        self.device = device
+        self.fno = FNO3d(modes=modes, width=width, n_layers=self.fno_layers, input_dim=width,
+                         output_dim=output_dim, device=self.device)
+
+    def forward(self, x, grid, bag_idx=None):
+        """x (B, T, Nx, Ny, Nz), grid (Nx, Ny, Nz, 3) -> (B, Nx, Ny, Nz, output_dim).  Composed as
+        NIOFP2D: the DeepONet combiner fused with the bag mean (ops.DeepONetBagFn), the
+        fixed-weight fc0 on [grid, ubar] (ops.BagMeanFn with d = 3), then FNO3d."""
+        ops.require_device(x, grid)
+        if x.dim() != 5 or tuple(grid.shape) != (*x.shape[2:], 3):
+            raise ValueError(f"NIOFP3D: expected x (B, T, Nx, Ny, Nz) and grid (Nx, Ny, Nz, 3), got "
+                             f"{tuple(x.shape)} and {tuple(grid.shape)}")
+        x, L, _ = _select(self, x, bag_idx)        # no dedup: the branch is BatchNorm'd
+        B, _, nx, ny, nz = x.shape
+        S = nx * ny * nz
+        w = self.deeponet.branch(x.unsqueeze(2))                   # (B, L, n_basis)
+        basis = self.deeponet.trunk(grid.reshape(-1, 3))           # (S, n_basis)
+        ubar = ops.DeepONetBagFn.apply(w, basis, self.deeponet.b0)
+        h = ops.BagMeanFn.apply(ubar.view(B, 1, S), grid.reshape(S, 3), self.fc0.weight.data,
+                                self.fc0.bias.data, None)
+        return self.fno(h.view(B, nx, ny, nz, -1))
 
 
 class NIOFP(nn.Module):

@@ -2356,6 +2356,71 @@ def conv2d(x, weight, bias, stride, padding):
     return Conv2dFn.apply(x, weight, bias, tuple(stride), tuple(padding))
 
 
+class Conv3dFn(torch.autograd.Function):
+    """nn.Conv3d (bias, groups 1, zero padding) of the NIOFP3D encoders' ConvBlock3D layers
+    (2d_FPE/Baselines.py:26-38) on the HIP implicit-GEMM kernels (csrc/conv3d.hip): x (N, Ci, D, H,
+    W), weight (Co, Ci, KD, KH, KW), bias (Co) -> (N, Co, Do, Ho, Wo).  Deterministic; any batch
+    size N and graph-capturable like Conv2dFn (every scratch comes from the caching allocator,
+    the split counts are host-side queries)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, padding):
+        require_device(x, weight)
+        x, weight = _c(x), _c(weight)
+        bias = _c(bias) if bias is not None else None
+        N, Ci, Di, Hi, Wi = x.shape
+        Co, Cw, KD, KH, KW = weight.shape
+        if Cw != Ci:
+            raise BlindnoError(f"conv3d: input has {Ci} channels, weight expects {Cw}")
+        g = (N, Ci, Di, Hi, Wi, Co, KD, KH, KW, *stride, *padding)
+        out = [(i + 2 * p - k) // s + 1 for i, k, s, p in zip((Di, Hi, Wi), (KD, KH, KW), stride, padding)]
+        ns = query("blindno_conv3d_fwd_nsplit", *g)      # split K for the few-voxel last blocks
+        if ns < 1:
+            raise BlindnoError(f"conv3d: invalid geometry {g} (output extents {out})")
+        y = _empty(N, Co, *out, like=x)
+        part = _empty(ns, y.numel(), like=x) if ns > 1 else None
+        call("blindno_conv3d_fwd", ptr(x), ptr(weight), ptr(bias), ptr(y), ptr(part), ns, *g,
+             stream_ptr())
+        ctx.geom = g
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        g = ctx.geom
+        N, Ci, Di, Hi, Wi, Co, KD, KH, KW = g[:9]
+        dy = _c(dy)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            ns = query("blindno_conv3d_bwd_data_nsplit", *g)
+            if ns < 1:
+                raise BlindnoError(f"conv3d: no input gradient for strides {g[9:12]} "
+                                   "(at most 8 stride-phase classes)")
+            dx = _empty(N, Ci, Di, Hi, Wi, like=dy)
+            part = _empty(ns, dx.numel(), like=dy) if ns > 1 else None
+            call("blindno_conv3d_bwd_data", ptr(dy), ptr(weight), ptr(dx), ptr(part), ns, *g,
+                 stream_ptr())
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            ncol = Ci * KD * KH * KW + 1
+            ns = query("blindno_conv3d_wgrad_nsplit", *g)
+            dwb = _empty(Co, ncol, like=dy)
+            part = _empty(ns, Co * ncol, like=dy) if ns > 1 else None
+            call("blindno_conv3d_bwd_weight", ptr(dy), ptr(x), ptr(dwb), ptr(part), ns, *g, stream_ptr())
+            dw = dwb[:, :-1].reshape(Co, Ci, KD, KH, KW) if ctx.needs_input_grad[1] else None
+            db = dwb[:, -1].contiguous() if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return dx, dw, db, None, None
+
+
+def _triple(v):
+    return (int(v),) * 3 if isinstance(v, int) else tuple(int(a) for a in v)
+
+
+def conv3d(x, weight, bias, stride, padding):
+    return Conv3dFn.apply(x, weight, bias, _triple(stride), _triple(padding))
+
+
 def linear(x, weight, bias):
     """nn.Linear on libblindno: x (..., K) @ weight (N, K)^T + bias as a 1x1 convolution of
     (rows, K, 1, 1) images (csrc/conv.hip implicit GEMMs: fp32 matrix cores, the bias a GEMM
@@ -2372,7 +2437,8 @@ class BNActFn(torch.autograd.Function):
     """BatchNorm2d + LeakyReLU of a ConvBlock (2d_FPE/Baselines.py:40-52) on rows [0, n) of z
     (rows [n, Npad) are the convolution chunks' padding and come out 0).  Running statistics
     are updated like torch.nn.BatchNorm2d (momentum, or the cumulative average when momentum
-    is None)."""
+    is None).  z may be (N, C, H, W) or the (N, C, D, H, W) of a ConvBlock3D with a BatchNorm3d:
+    the kernel sees (N, C, HW) with HW the voxels of one channel plane."""
 
     @staticmethod
     def forward(ctx, z, gamma, beta, bn, n, slope):

@@ -52,7 +52,7 @@ def build(force: bool = False, jobs: int = 8, verbose: bool = True) -> str:
     hipcc = _hipcc()
     os.makedirs(BUILD, exist_ok=True)
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
-    headers = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(INCLUDE, "blindno.h")]
+    headers = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(INCLUDE, "*.h"))
     objs = []
     todo = []
     for s in srcs:
@@ -96,7 +96,7 @@ def build_cabi_test(hipcc: str, force: bool = False, verbose: bool = True) -> st
     GPU box as a whole)."""
     if not os.path.exists(CABI_SRC):
         return ""
-    if not force and not _newer([CABI_SRC, OUT, os.path.join(INCLUDE, "blindno.h")], CABI_BIN):
+    if not force and not _newer([CABI_SRC, OUT, *glob.glob(os.path.join(INCLUDE, "*.h"))], CABI_BIN):
         return CABI_BIN
     rel = os.path.relpath(os.path.dirname(OUT), os.path.dirname(CABI_BIN))
     cmd = [hipcc, "-O2", "-std=c++17", f"--offload-arch={ARCH}", "-I", INCLUDE, CABI_SRC,

@@ -891,5 +891,6 @@ int blindno_project3d_bwd(const float* z, const float* w1, const float* b1, cons
 #endif
 
 #include "blindno_conv3d.h"
+#include "blindno_fpe.h"
 
 #endif /* BLINDNO_H */

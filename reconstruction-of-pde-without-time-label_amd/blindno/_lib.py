@@ -190,8 +190,15 @@ SIGNATURES_CONV3D = {
     "blindno_conv3d_bwd_weight": "pppp" + "i" + "i" * 15 + "s",
 }
 
+# include/blindno_fpe.h: the grid-resident Fokker-Planck propagator (csrc/fpe_nd.hip)
+SIGNATURES_FPE = {
+    "blindno_fp_propagate_nd_scratch_doubles": "iiii",
+    "blindno_fp_propagate_nd": "pppp" + "iiiiiii" + "d" + "s",
+}
+
 # entry points returning int64_t (byte counts) instead of an error code / int count
-RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))}
+RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))} | \
+    {n for n in SIGNATURES_FPE if n.endswith("_doubles")}
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_int64, "f": ctypes.c_float,
        "d": ctypes.c_double, "s": ctypes.c_void_p}
@@ -216,7 +223,7 @@ def load():
                 "`python reconstruction-of-pde-without-time-label_amd/build.py` "
                 "(there is no CPU fallback)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in {**SIGNATURES, **SIGNATURES_CONV3D}.items():
+        for name, sig in {**SIGNATURES, **SIGNATURES_CONV3D, **SIGNATURES_FPE}.items():
             fn = getattr(lib, name)
             fn.argtypes = [_CT[c] for c in sig]
             fn.restype = ctypes.c_int64 if name in RET64 else ctypes.c_int
@@ -227,7 +234,7 @@ def load():
 
 
 def exported_symbols():
-    return list(SIGNATURES) + list(SIGNATURES_CONV3D) + ["blindno_error_string"]
+    return list(SIGNATURES) + list(SIGNATURES_CONV3D) + list(SIGNATURES_FPE) + ["blindno_error_string"]
 
 
 def stream_ptr(device=None):

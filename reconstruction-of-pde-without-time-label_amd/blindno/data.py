@@ -8,6 +8,8 @@ Reference Dataset classes (defined inside the flat train scripts):
   TrajectoryDataset2DForce  2d_Non_conservative_FPE/train_fno.py:13-60 (the reference also names
                             it TrajectoryDataset2D; npz keys trajectories, F (M, 2, Nx, Ny);
                             F scale 1e12; item y = F.permute(1, 2, 0))
+  TrajectoryDataset3D       (no reference class) TrajectoryDataset2D with one more axis, for the
+                            bags of datagen.fpe_3d_dataset; item y = (Nx, Ny, Nz, 2)
   TrajectoryDataset1D       1d_FPE/train_fno.py:8-58   (scales 1e5 / 1e20 / 1e5; drag (M,) is
                             a scalar repeated over x; item y = stack(potential, drag) (Nx, 2))
   ParameterDataset          1d_GPE/train_fno_GPE.py:33-74 (np.save'd dict y, g, kappa, V;
@@ -55,6 +57,17 @@ class TrajectoryDataset2D(Dataset):
 
     def targets(self) -> np.ndarray:
         return np.stack([self.potential, self.drag], axis=-1)
+
+
+class TrajectoryDataset3D(TrajectoryDataset2D):
+    """3D FPE bags (datagen.fpe_3d_dataset; no reference class): TrajectoryDataset2D with one more
+    axis -- the same scales and z-scoring; item x = (T, Nx, Ny, Nz), y = (Nx, Ny, Nz, 2)."""
+
+    def __getitem__(self, idx):
+        x = torch.tensor(self.trajectories[idx], dtype=torch.float32)
+        y = torch.stack((torch.tensor(self.potential[idx], dtype=torch.float32),
+                         torch.tensor(self.drag[idx], dtype=torch.float32)), dim=-1)
+        return x, y
 
 
 class TrajectoryDataset2DForce(Dataset):

@@ -20,7 +20,10 @@ scipy.sparse.linalg.expm_multiply on the oracle's independently assembled matrix
 
 The rate construction (setup, O(N)) is host numpy; the propagation -- the hot part, N cells x
 Nsteps x substeps x Taylor degree stencil passes -- is ``blindno_fp_propagate``, one
-LDS-resident workgroup per trajectory, many trajectories per launch (``propagate_many``).
+LDS-resident workgroup per trajectory, many trajectories per launch (``propagate_many``), for 1D
+and 2D grids of at most 8192 cells, and ``blindno_fp_propagate_nd`` for larger ones and for 3D
+grids: the density stays in global memory and every Horner pass is one launch
+(tests/test_fpe_nd.py, tests/test_gpu_fpe_nd.py against tests/fpe3d_ref.py).
 """
 from __future__ import annotations
 
@@ -31,7 +34,7 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 import torch
 
-from ._lib import BlindnoError, call, ptr, stream_ptr
+from ._lib import BlindnoError, call, ptr, query, stream_ptr
 
 K_B = 1.380649e-23          # scipy.constants.k
 TAYLOR_DEGREE = 18          # truncation (1/2)^19 / 19! ~ 1e-23 per substep at theta = 1/2
@@ -85,8 +88,9 @@ def potential_from_data(grid, data):
     g = np.asarray(grid, dtype=np.float64)
     if data.ndim == 1:
         axes = (g.reshape(-1),)
-    elif g.ndim == data.ndim + 1:                  # simulator grid (ndim, Nx, Ny)
-        axes = (g[0][:, 0], g[1][0, :])
+    elif g.ndim == data.ndim + 1:                  # simulator grid (ndim, Nx, Ny[, Nz])
+        nd = data.ndim                             # axis d varies along dimension d only
+        axes = tuple(g[d][tuple(slice(None) if a == d else 0 for a in range(nd))] for d in range(nd))
     else:                                          # a sequence of axes
         axes = tuple(np.asarray(a, dtype=np.float64) for a in grid)
     f = RegularGridInterpolator(axes, data, bounds_error=False, fill_value=None)
@@ -109,8 +113,8 @@ class fokker_planck:
                  force: Optional[Callable] = None, boundary=boundary.reflecting):
         self.extent = np.atleast_1d(np.asarray(extent, dtype=np.float64))
         self.ndim = self.extent.size
-        if self.ndim not in (1, 2):
-            raise BlindnoError("fokker_planck: 1D or 2D grids")
+        if self.ndim not in (1, 2, 3):
+            raise BlindnoError("fokker_planck: 1D, 2D or 3D grids")
         self.resolution = np.broadcast_to(np.asarray(resolution, dtype=np.float64), (self.ndim,)).copy()
         self.temperature = float(temperature)
         self.beta = 1.0 / (K_B * self.temperature)
@@ -167,10 +171,29 @@ class fokker_planck:
             c[2 + 2 * i] = _roll(self.L[i], -1, i).reshape(-1)    # from i + e, hopping left
         return c
 
+    def coefficients_nd(self) -> np.ndarray:
+        """(7, N) float64 [diag, cxm, cxp, cym, cyp, czm, czp] of blindno_fp_propagate_nd
+        (in-rates; the rows of an absent axis are zero)."""
+        N = int(np.prod(self.Ngrid))
+        c = np.zeros((7, N))
+        diag = sum(self.R[i] + self.L[i] for i in range(self.ndim))
+        c[0] = diag.reshape(-1)
+        for i in range(self.ndim):
+            c[1 + 2 * i] = _roll(self.R[i], 1, i).reshape(-1)
+            c[2 + 2 * i] = _roll(self.L[i], -1, i).reshape(-1)
+        return c
+
     def grid_dims(self):
+        if self.ndim == 3:
+            raise BlindnoError("grid_dims: a 3D grid has no (nx, ny); use grid_dims_nd")
         nx = int(self.Ngrid[0])
         ny = int(self.Ngrid[1]) if self.ndim == 2 else 1
         return nx, ny
+
+    def grid_dims_nd(self):
+        """(nx, ny, nz) with 1 for the absent axes."""
+        n = [int(v) for v in self.Ngrid] + [1] * (3 - self.ndim)
+        return n[0], n[1], n[2]
 
     def propagate_interval(self, initial, tf, Nsteps=None, dt=None, normalize=True, device="cuda"):
         """(time (Nsteps,), Pt (Nsteps, *Ngrid)): exp(M t) p0 at t = linspace(0, tf, Nsteps)."""
@@ -184,10 +207,22 @@ class fokker_planck:
 # the kernel's int argument); such a request is refused before launching.
 MAX_TOTAL_SUBSTEPS = 1 << 24
 
+# Largest grid of the LDS-resident kernel (blindno_fp_propagate: one trajectory per workgroup);
+# larger 1D / 2D grids and every 3D grid go to the grid-resident blindno_fp_propagate_nd.
+LDS_MAX_CELLS = 8192
+
+# The grid-resident path enqueues one kernel per Horner pass, (Nsteps - 1) x substeps x degree of
+# them per substep group, so its budget is counted in passes and a request above it is refused
+# before launching.  Measured 8.315 us per pass at 40^3, B = 8 (profiles/fpe_nd_bench.json):
+# 120 s / 8.315 us = 14.4 M passes, so 2^23 passes (69.8 s there) is the largest power of two whose
+# worst case stays under 120 s (2^24: 139.5 s).  A pass streams 80 B per cell at ~4.9 TB/s, so a
+# larger batch or grid takes proportionally longer per pass.
+MAX_TOTAL_PASSES_ND = 1 << 23
+
 
 def substeps_for(coef: np.ndarray, dt_out: float, theta: float = THETA) -> int:
     """Substeps per output interval so that ||h M||_1 <= theta (||M||_1 = 2 max diag) for the
-    rate coefficients ``coef`` (5, N) of one trajectory (or a stack: the max over it)."""
+    rate coefficients ``coef`` (5, N) or (7, N) of one trajectory (or a stack: the max over it)."""
     norm = 2.0 * float(np.max(coef[..., 0, :]))
     if not math.isfinite(norm):
         raise BlindnoError("fp propagation: non-finite hop rates (overflowing exp(-beta dU/2))")
@@ -196,26 +231,31 @@ def substeps_for(coef: np.ndarray, dt_out: float, theta: float = THETA) -> int:
 
 def propagate_many(sims: Sequence[fokker_planck], initials, tf, Nsteps=None, dt=None,
                    normalize=True, device="cuda", select=None):
-    """propagate_interval of several simulators (same grid) in ONE launch: one workgroup per
-    trajectory.  Returns [(time, Pt)] in the order given; ``select`` (per trajectory, a list of
-    time indices) keeps only those records (gathered on the device before the host copy)."""
+    """propagate_interval of several simulators (same grid) batched on the device.  1D / 2D
+    grids of at most LDS_MAX_CELLS cells run on blindno_fp_propagate (one workgroup per
+    trajectory, one launch per substep group); larger ones and every 3D grid on
+    blindno_fp_propagate_nd (grid-resident, one launch per Horner pass).  Returns [(time, Pt)]
+    in the order given; ``select`` (per trajectory, a list of time indices) keeps only those
+    records (gathered on the device before the host copy)."""
     if not sims:
         return []
     if Nsteps is None:
         Nsteps = int(np.ceil(tf / dt))
     Nsteps = int(Nsteps)
-    nx, ny = sims[0].grid_dims()
-    N = nx * ny
+    dims = sims[0].grid_dims_nd()
+    nx, ny, nz = dims
+    N = nx * ny * nz
+    nd_path = sims[0].ndim == 3 or N > LDS_MAX_CELLS
     p0 = np.zeros((len(sims), N))
-    coef = np.zeros((len(sims), 5, N))
+    coef = np.zeros((len(sims), 7 if nd_path else 5, N))
     for k, (sim, ini) in enumerate(zip(sims, initials)):
-        if sim.grid_dims() != (nx, ny):
+        if sim.grid_dims_nd() != dims or sim.ndim != sims[0].ndim:
             raise BlindnoError("propagate_many: every simulator needs the same grid")
         v = np.asarray(ini(*sim.grid) if callable(ini) else ini, dtype=np.float64).reshape(-1)
         if normalize:
             v = v / np.sum(v)
         p0[k] = v
-        coef[k] = sim.coefficients()
+        coef[k] = sim.coefficients_nd() if nd_path else sim.coefficients()
     time = np.linspace(0, tf, Nsteps)
     dt_out = tf / (Nsteps - 1) if Nsteps > 1 else 0.0
     # substeps per trajectory: one stiff trajectory must not multiply every other one's work, so
@@ -229,6 +269,16 @@ def propagate_many(sims: Sequence[fokker_planck], initials, tf, Nsteps=None, dt=
             f"({worst * (Nsteps - 1)} in total, limit {MAX_TOTAL_SUBSTEPS}); its hop rates reach "
             f"{float(np.max(coef[k, 0])):.3e}/s -- a force / potential far outside the physical "
             f"range (e.g. a badly predicted field); refusing to launch")
+    passes = sum(set(steps)) * max(0, Nsteps - 1) * TAYLOR_DEGREE
+    if nd_path and passes > MAX_TOTAL_PASSES_ND:
+        k = int(np.argmax(steps))
+        raise BlindnoError(
+            f"fp propagation: {nx} x {ny} x {nz} cells run one kernel per Horner pass, and this "
+            f"request needs {passes} passes ({Nsteps - 1} output intervals x the substep counts "
+            f"{sorted(set(steps))} x degree {TAYLOR_DEGREE}; limit {MAX_TOTAL_PASSES_ND}); "
+            f"trajectory {k} needs {worst} substeps per interval, its hop rates reach "
+            f"{float(np.max(coef[k, 0])):.3e}/s -- record fewer or closer times, or check the "
+            f"force / potential; refusing to launch")
     dev = torch.device(device)
     if dev.type != "cuda":
         raise BlindnoError("fp propagation runs on a HIP device (there is no CPU path)")
@@ -238,8 +288,14 @@ def propagate_many(sims: Sequence[fokker_planck], initials, tf, Nsteps=None, dt=
         p0_d = torch.from_numpy(np.ascontiguousarray(p0[ks])).to(dev)
         coef_d = torch.from_numpy(np.ascontiguousarray(coef[ks])).to(dev)
         dst = out if len(ks) == len(sims) else torch.empty(len(ks), Nsteps, N, dtype=torch.float64, device=dev)
-        call("blindno_fp_propagate", ptr(p0_d), ptr(coef_d), ptr(dst), len(ks), nx, ny, Nsteps, s,
-             TAYLOR_DEGREE, float(dt_out), stream_ptr(dev))
+        if nd_path:
+            scratch = torch.empty(query("blindno_fp_propagate_nd_scratch_doubles", len(ks), nx, ny, nz),
+                                  dtype=torch.float64, device=dev)
+            call("blindno_fp_propagate_nd", ptr(p0_d), ptr(coef_d), ptr(dst), ptr(scratch), len(ks),
+                 nx, ny, nz, Nsteps, s, TAYLOR_DEGREE, float(dt_out), stream_ptr(dev))
+        else:
+            call("blindno_fp_propagate", ptr(p0_d), ptr(coef_d), ptr(dst), len(ks), nx, ny, Nsteps, s,
+                 TAYLOR_DEGREE, float(dt_out), stream_ptr(dev))
         if dst is not out:
             out[torch.as_tensor(ks, device=dev)] = dst
     grid_shape = tuple(int(n) for n in sims[0].Ngrid)

@@ -1,0 +1,159 @@
+"""3D Fokker-Planck rates, the (7, N) coefficient table of blindno_fp_propagate_nd, its binding, the
+launch budget of the grid-resident path and TrajectoryDataset3D (no GPU needed).
+
+PARITY UNPINNED as in tests/test_fpe.py (fplanck is absent, and the reference has no 3D generator at
+all): the checker is tests/fpe3d_ref.py's independent sparse assembly of the same master equation
+and its physical invariants (mass conservation, the Boltzmann stationary state).
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import fpe3d_ref
+from conftest import ROOT
+from fpe3d_ref import NM, make_sim
+
+
+@pytest.mark.parametrize("dims,periodic", [((5, 4, 3), (True, True, True)),
+                                           ((7, 6, 5), (False, False, False)),
+                                           ((4, 5, 6), (False, True, False))])
+def test_3d_rates_match_independent_assembly(dims, periodic):
+    sim = make_sim(dims, periodic)
+    assert sim.ndim == 3 and sim.grid_dims_nd() == dims
+    c = sim.coefficients_nd()
+    assert c.shape == (7, int(np.prod(dims)))
+    M = fpe3d_ref.dense_from_coefficients_nd(c, dims)
+    Mo = fpe3d_ref.matrix_of(sim).toarray()
+    assert np.abs(M - Mo).max() <= 1e-12 * np.abs(Mo).max()
+    # column sums: what leaves a cell arrives at its neighbours (mass conservation)
+    assert np.abs(M.sum(axis=0)).max() <= 1e-12 * np.abs(np.diag(M)).max()
+    assert np.abs(np.asarray(fpe3d_ref.matrix_of(sim).sum(axis=0))).max() <= 1e-12 * np.abs(np.diag(Mo)).max()
+
+
+def test_3d_boltzmann_state_is_stationary():
+    """A pure potential between reflecting walls: exp(-beta U) is stationary under the (7, N)
+    coefficients and detailed balance holds."""
+    from blindno import fpe
+    kT = fpe.K_B * 300.0
+    U = lambda x, y, z: 1.5 * kT * np.cos(x / (20 * NM)) * np.sin(y / (15 * NM) + 0.3) + 0.8 * kT * (z / (30 * NM)) ** 2  # noqa: E731
+    sim = fpe.fokker_planck(temperature=300, drag=2e-9, extent=[65 * NM, 55 * NM, 45 * NM], resolution=10 * NM,
+                            potential=U, boundary=fpe.boundary.reflecting)
+    dims = sim.grid_dims_nd()
+    assert dims == (7, 6, 5)
+    M = fpe3d_ref.dense_from_coefficients_nd(sim.coefficients_nd(), dims)
+    pb = np.exp(-sim.beta * sim.potential_values).reshape(-1)
+    pb /= pb.sum()
+    assert np.abs(M @ pb).max() <= 1e-10 * np.abs(np.diag(M)).max() * pb.max()
+    flux = M * pb[None, :]
+    off = flux - np.diag(np.diag(flux))
+    assert np.abs(off - off.T).max() <= 1e-12 * np.abs(off).max()
+
+
+@pytest.mark.parametrize("dims", [(9, 1, 1), (6, 7, 1)])
+def test_coefficients_nd_of_lower_dimensions(dims):
+    """1D / 2D simulators: coefficients_nd is coefficients() plus zero rows for the absent axes,
+    and grid_dims_nd pads grid_dims with 1."""
+    sim = make_sim(dims, (False, True, False))
+    c5, c7 = sim.coefficients(), sim.coefficients_nd()
+    assert c7.shape == (7, c5.shape[1])
+    assert np.array_equal(c7[:5], c5) and not c7[5:].any()
+    assert sim.grid_dims_nd() == dims and sim.grid_dims_nd()[:2] == sim.grid_dims()
+    if sim.ndim == 1:
+        assert not c7[3:].any()
+
+
+def test_potential_from_data_on_a_3d_grid():
+    from blindno import fpe
+    sim = make_sim((5, 4, 3), (False, False, False))
+    assert sim.grid.shape == (3, 5, 4, 3)
+    f = fpe.potential_from_data(sim.grid, sim.potential_values)
+    assert np.allclose(f(*sim.grid), sim.potential_values, rtol=1e-12, atol=0)
+    sim2 = fpe.fokker_planck(temperature=300, drag=sim.drag, extent=sim.extent, resolution=10 * NM, potential=f)
+    assert np.allclose(sim2.potential_values, sim.potential_values, rtol=1e-12, atol=0)
+
+
+def test_fpe_symbols_declared_and_bound():
+    """include/blindno_fpe.h (included by blindno.h) <=> _lib.SIGNATURES_FPE <=> the library."""
+    import blindno
+    from blindno import _lib
+    assert '#include "blindno_fpe.h"' in open(os.path.join(ROOT, "include", "blindno.h")).read()
+    hdr = open(os.path.join(ROOT, "include", "blindno_fpe.h")).read()
+    decl = sorted(set(re.findall(r"^(?:int|int64_t|const char\*)\s+(blindno_\w+)\(", hdr, re.M)))
+    assert decl == sorted(_lib.SIGNATURES_FPE) and len(decl) == 2
+    assert not set(_lib.SIGNATURES_FPE) & (set(_lib.SIGNATURES) | set(_lib.SIGNATURES_CONV3D))
+    lib = blindno.load_library()
+    for s in decl:
+        assert hasattr(lib, s) and s in _lib.exported_symbols(), s
+        m = re.search(r"\b(?:int|int64_t)\s+" + s + r"\s*\(([^;]*)\)\s*;", hdr)
+        nargs = len([a for a in m.group(1).split(",") if a.strip()])
+        assert nargs == len(_lib.SIGNATURES_FPE[s]) == len(getattr(lib, s).argtypes), (s, nargs)
+    # the host-only size query: two iterates per cell, int64, -1 for a refused grid
+    q = lambda *a: _lib.query("blindno_fp_propagate_nd_scratch_doubles", *a)   # noqa: E731
+    assert q(8, 40, 40, 40) == 2 * 8 * 64000
+    assert q(600, 2048, 2048, 1) == 2 * 600 * 2048 * 2048 > 2 ** 32
+    assert q(1, 1 << 11, 1 << 11, 1) > 0            # 2^22 cells are inside the documented limit
+    for bad in [(0, 4, 4, 4), (1, 0, 4, 4), (1, 4, 0, 4), (1, 4, 4, 0), (1, 1 << 20, 1 << 20, 1 << 20),
+                (1, 2 ** 31 - 1, 2 ** 31 - 1, 2 ** 31 - 1)]:
+        assert q(*bad) == -1, bad
+    src = open(os.path.join(ROOT, "reconstruction-of-pde-without-time-label_amd", "csrc", "fpe_nd.hip")).read()
+    assert "atomic" not in src.lower() and "hipLaunchCooperativeKernel" not in src
+
+
+def test_over_budget_request_is_refused_before_launch():
+    """The grid-resident path costs one launch per Horner pass: a request above
+    MAX_TOTAL_PASSES_ND raises before anything touches the device (device='cpu' would raise the
+    no-CPU-path error next), while the same interval on a grid the LDS kernel runs passes this
+    check."""
+    from blindno import fpe
+    from blindno._lib import BlindnoError
+    assert fpe.MAX_TOTAL_PASSES_ND < fpe.MAX_TOTAL_SUBSTEPS and fpe.MAX_TOTAL_PASSES_ND & (fpe.MAX_TOTAL_PASSES_ND - 1) == 0
+    sim = make_sim((5, 4, 3), (True, True, True))
+    p0 = fpe3d_ref.initial(sim)
+    per = fpe.substeps_for(sim.coefficients_nd(), 1.0)              # substeps per second of interval
+    want = fpe.MAX_TOTAL_PASSES_ND // (2 * fpe.TAYLOR_DEGREE) + 2   # substeps per interval, 2 intervals
+    tf = 2 * want / per
+    assert 2 * fpe.substeps_for(sim.coefficients_nd(), tf / 2) < fpe.MAX_TOTAL_SUBSTEPS
+    with pytest.raises(BlindnoError, match=r"passes.*refusing to launch"):
+        fpe.propagate_many([sim], [p0], tf, Nsteps=3, device="cpu")
+    with pytest.raises(BlindnoError, match="no CPU path"):         # just inside the budget
+        fpe.propagate_many([sim], [p0], tf / 2.2, Nsteps=3, device="cpu")
+    flat = make_sim((5, 4, 1), (True, True, False))
+    with pytest.raises(BlindnoError, match="no CPU path"):         # LDS kernel: one launch
+        fpe.propagate_many([flat], [fpe3d_ref.initial(flat)], tf, Nsteps=3, device="cpu")
+
+
+def test_trajectory_dataset_3d():
+    from blindno import data
+    rs = np.random.RandomState(3)
+    M, T, S = 4, 5, (6, 5, 4)
+    arrays = dict(trajectories=rs.rand(M, T, *S) * 1e-10, potential=rs.randn(M, *S) * 1e-21,
+                  drag=rs.rand(M, *S) * 1e-6 + 1e-6)
+    ds = data.TrajectoryDataset3D(arrays=arrays)
+    assert len(ds) == M
+    x, y = ds[1]
+    assert x.shape == (T, *S) and y.shape == (*S, 2) and x.dtype == y.dtype == torch.float32
+    assert torch.equal(y[..., 0], torch.tensor(ds.potential[1])) and torch.equal(y[..., 1], torch.tensor(ds.drag[1]))
+    # the 2D class's scalings and z-scoring: trajectories over (sample, time), targets over samples
+    tr = np.array(arrays["trajectories"], dtype=np.float32) * 1e10
+    assert ds.trajectories_mean.shape == (1, 1, *S) and ds.potential_mean.shape == (1, *S)
+    assert np.array_equal(ds.trajectories, (tr - tr.mean((0, 1), keepdims=True)) / (tr.std((0, 1), keepdims=True) + 1e-8))
+    assert np.abs(ds.trajectories.mean((0, 1))).max() < 1e-5 and np.abs(ds.trajectories.std((0, 1)) - 1).max() < 1e-3
+    for a in (ds.potential, ds.drag):
+        assert np.abs(a.mean(0)).max() < 1e-5 and np.abs(a.std(0) - 1).max() < 1e-3
+    assert ds.targets().shape == (M, *S, 2)
+    X, Y = data.device_tensors(ds, [0, 2], device="cpu")
+    assert X.shape == (2, T, *S) and Y.shape == (2, *S, 2)
+
+
+def test_short_time_grids_record_every_step():
+    """The generators record min(100, nsteps) times; at nsteps >= 100 the draw is the reference's."""
+    from blindno import datagen
+    np.random.seed(1)
+    assert np.array_equal(datagen._select(3), [0, 1, 2])
+    np.random.seed(2)
+    a = datagen._select(120)
+    np.random.seed(2)
+    assert np.array_equal(a, np.sort(np.random.choice(range(120), size=100, replace=False)))

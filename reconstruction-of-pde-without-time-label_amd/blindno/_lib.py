@@ -196,9 +196,19 @@ SIGNATURES_FPE = {
     "blindno_fp_propagate_nd": "pppp" + "iiiiiii" + "d" + "s",
 }
 
+# include/blindno_gpe2d.h: the grid-resident 2D GPE solver and the 2D trapezoid residual
+# (csrc/gpe2d.hip)
+SIGNATURES_GPE2D = {
+    "blindno_gpe2d_scratch_doubles": "iii",
+    "blindno_gpe2d_launches": "ii",
+    "blindno_gpe2d_solve": "pppp" + "ddd" + "iii" + "pipp" + "p" + "iiii" + "s",
+    "blindno_trapz2_frames": "ppppp" + "iii" + "s",
+}
+
 # entry points returning int64_t (byte counts) instead of an error code / int count
 RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))} | \
-    {n for n in SIGNATURES_FPE if n.endswith("_doubles")}
+    {n for n in SIGNATURES_FPE if n.endswith("_doubles")} | \
+    {n for n in SIGNATURES_GPE2D if n.endswith(("_doubles", "_launches"))}
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_int64, "f": ctypes.c_float,
        "d": ctypes.c_double, "s": ctypes.c_void_p}
@@ -223,7 +233,7 @@ def load():
                 "`python reconstruction-of-pde-without-time-label_amd/build.py` "
                 "(there is no CPU fallback)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in {**SIGNATURES, **SIGNATURES_CONV3D, **SIGNATURES_FPE}.items():
+        for name, sig in {**SIGNATURES, **SIGNATURES_CONV3D, **SIGNATURES_FPE, **SIGNATURES_GPE2D}.items():
             fn = getattr(lib, name)
             fn.argtypes = [_CT[c] for c in sig]
             fn.restype = ctypes.c_int64 if name in RET64 else ctypes.c_int
@@ -234,7 +244,8 @@ def load():
 
 
 def exported_symbols():
-    return list(SIGNATURES) + list(SIGNATURES_CONV3D) + list(SIGNATURES_FPE) + ["blindno_error_string"]
+    return (list(SIGNATURES) + list(SIGNATURES_CONV3D) + list(SIGNATURES_FPE) + list(SIGNATURES_GPE2D) +
+            ["blindno_error_string"])
 
 
 def stream_ptr(device=None):

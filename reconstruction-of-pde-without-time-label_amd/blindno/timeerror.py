@@ -1,8 +1,8 @@
 """Density-trajectory errors of predicted fields: 2d_Non_conservative_FPE/
 compute_time_error.py:361-510 (``compute_time_error``, FPE forces), 1d_FPE/
 compute_time_error.py:215-420 (``compute_time_error_1d``, potential + drag) and 1d_GPE/
-compute_time_error_GPE.py:208-330 (``compute_time_error_gpe``, GPE potentials), each as one
-batched pipeline.
+compute_time_error_GPE.py:208-330 (``compute_time_error_gpe``, GPE potentials; its 2D
+counterpart ``compute_time_error_gpe_2d`` is the project's own), each as one batched pipeline.
 
 Per test index the reference normalises the bag with the train statistics, predicts (Fx, Fy)
 with each model, de-normalises, propagates a Gaussian density (centre (-150, -150) nm, width
@@ -148,6 +148,69 @@ def compute_time_error_gpe(models: Dict[str, torch.nn.Module], train, test, indi
                 os.makedirs(d, exist_ok=True)
                 np.save(os.path.join(d, f"sample_{i}_V_and_err.npy"),
                         {"x": x, "true_V": V[k * per], "pred_V": V[k * per + 1 + j], "g": g[k * per],
+                         "kappa": kappa[k * per], "Err_L2_rel": e})
+    out = {name: np.array(v, dtype=float) for name, v in errs.items()}
+    if outdir is not None:
+        for name, arr in out.items():
+            np.save(os.path.join(outdir, f"ErrL2_relative_{name}_Nsamples_{len(idx)}.npy"), arr)
+    return out
+
+
+# ------------------------------------------------------------------------------- 2D GPE
+def compute_time_error_gpe_2d(models: Dict[str, torch.nn.Module], train, test, indices: Iterable[int],
+                              outdir: Optional[str] = None, order: int = 2, dt: float = 0.005,
+                              t_final: float = 5.0, init_ic: int = 2, batch: int = 4, rec_every: int = 10,
+                              device="cuda") -> Dict[str, np.ndarray]:
+    """The 2D counterpart of ``compute_time_error_gpe`` for the 2d_GPE experiment (the
+    project's own; ``train`` / ``test`` are blindno.gpe.generate_training_data_2d dicts): per
+    test index, V predicted by each model (de-normalised with the train V_max), |psi| propagated
+    from psi0 = ic(x) ic(y) on [-10, 10]^2 under the true V and under each prediction (true g,
+    kappa), and time_averaged_L2_error_2d of the densities.  All trajectories -- reference and
+    every model's, for every index -- run in ONE blindno.gpe.solve_batch_2d call, recording every
+    ``rec_every``-th step (a full 256^2 record of 1001 frames is 0.5 GB per trajectory; the call
+    refuses a record above gpe.MAX_RECORD_BYTES).  Returns {model: errors in index order}; with
+    ``outdir`` writes <outdir>/<model>/sample_<idx>_V_and_err.npy and
+    ErrL2_relative_<model>_Nsamples_<n>.npy as the 1D function does (x and y in the dict)."""
+    from . import gpe
+    sc = evaluate.compute_train_scalers_gpe(train)
+    tn = evaluate.normalize_gpe(test, sc)
+    yy = np.asarray(tn["y"])
+    idx = [int(i) for i in indices if 0 <= int(i) < yy.shape[0]]
+    if not idx:
+        return {name: np.zeros(0) for name in models}
+    nx, ny = yy.shape[2], yy.shape[3]
+    xin = torch.tensor(np.stack([yy[i] for i in idx]), dtype=torch.float32, device=device)
+    grid_n = evaluate.grid2d(nx, ny, device)
+    preds = {}
+    for name, m in models.items():
+        p = evaluate.predict(m, xin, grid_n, batch).cpu().numpy()
+        preds[name] = (p[..., 0] if p.ndim == 4 else p) * sc["V_max"]
+    x = np.linspace(-10, 10, nx)
+    y = np.linspace(-10, 10, ny)
+    V, g, kappa = [], [], []
+    for k, i in enumerate(idx):
+        gi = float(np.atleast_1d(test["g"][i])[0])
+        ki = float(np.atleast_1d(test["kappa"][i])[0])
+        for Vi in [tn["V"][i] * sc["V_max"]] + [preds[name][k] for name in models]:
+            V.append(Vi)
+            g.append(gi)
+            kappa.append(ki)
+    psi0 = gpe.initial_condition(init_ic, x)[:, None] * gpe.initial_condition(init_ic, y)[None, :]
+    r = gpe.solve_batch_2d(psi0, x, y, dt, t_final, order, np.array(g), np.array(kappa), np.array(V),
+                           rec_every=rec_every, device=device)
+    t, rho = r["t"], r["abs"]
+    per = 1 + len(models)
+    errs = {name: [] for name in models}
+    for k, i in enumerate(idx):
+        ref = rho[k * per]
+        for j, name in enumerate(models):
+            e = gpe.time_averaged_L2_error_2d(t, ref, t, rho[k * per + 1 + j], (x, y))
+            errs[name].append(e)
+            if outdir is not None:
+                d = os.path.join(outdir, name)
+                os.makedirs(d, exist_ok=True)
+                np.save(os.path.join(d, f"sample_{i}_V_and_err.npy"),
+                        {"x": x, "y": y, "true_V": V[k * per], "pred_V": V[k * per + 1 + j], "g": g[k * per],
                          "kappa": kappa[k * per], "Err_L2_rel": e})
     out = {name: np.array(v, dtype=float) for name, v in errs.items()}
     if outdir is not None:

@@ -140,6 +140,13 @@ def _experiments(model: str = "fno"):
         "1d_GPE": Experiment("1d_GPE", 1, data.ParameterDataset,
                              lambda n, dev: nio.NIOFP_FNO(3, 20, 40, 1, dev, heads=("fno_V",)), 1e-3, 32, 10,
                              "results_GPE_fno", False),
+        # the project's own experiment (the reference lists 2D GPE and ships no script for it):
+        # the 2D FPE configuration with the GPE dataset's single target V (blindno.gpe.
+        # generate_training_data_2d) and the GPE per-sample metric; NIO-FNO only
+        "2d_GPE": Experiment("2d_GPE", 2, data.ParameterDataset,
+                             lambda n, dev: nio.NIOFP2D_FNO(2, 3, 100, 25, 3, 12, 32, 1, heads=("fno_V",),
+                                                            branch_last_kernel=Encoder2D.kernel_for_grid(n)),
+                             5e-4, 4, 5, "results_2d_GPE_fno", False),
     }
 
 
@@ -328,12 +335,16 @@ def main(argv=None):
     ap.add_argument("--scheduler-mode", choices=["reference", "per-epoch"], default="reference")
     ap.add_argument("--eval-mode", choices=["reference", "global"], default="reference")
     a = ap.parse_args(argv)
+    exps = _experiments(a.model)
+    if a.experiment not in exps:
+        ap.error(f"--experiment {a.experiment} has no --model {a.model} configuration "
+                 f"(it has: {', '.join(m for m in ('fno', 'unet', 'nio') if a.experiment in _experiments(m))})")
+    exp = exps[a.experiment]
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1:
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     torch.cuda.set_device(local)
-    exp = _experiments(a.model)[a.experiment]
     t = Trainer(exp, a.data, a.outdir or exp.result_dir, torch.device("cuda", local), epochs=a.epochs,
                 seed=a.seed, split_seed=a.split_seed, scheduler_mode=a.scheduler_mode,
                 eval_mode=a.eval_mode, save_interval=a.save_interval, batch=a.batch, lr=a.lr,

@@ -205,10 +205,19 @@ SIGNATURES_GPE2D = {
     "blindno_trapz2_frames": "ppppp" + "iii" + "s",
 }
 
+# include/blindno_bag3d.h: the bag-level projection of the 3D snapshot encoder (csrc/bagproj3d.hip)
+SIGNATURES_BAG3D = {
+    "blindno_project_bag3d_stats_floats": "iiii",
+    "blindno_project_bag3d_bwd_nchunk": "iiii",
+    "blindno_project_bag3d_fwd": "ppppppppp" + "iiiiiiiiii" + "s",
+    "blindno_project_bag3d_bwd": "ppppppp" + "i" + "iiiiiiiiii" + "s",
+}
+
 # entry points returning int64_t (byte counts) instead of an error code / int count
 RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))} | \
     {n for n in SIGNATURES_FPE if n.endswith("_doubles")} | \
-    {n for n in SIGNATURES_GPE2D if n.endswith(("_doubles", "_launches"))}
+    {n for n in SIGNATURES_GPE2D if n.endswith(("_doubles", "_launches"))} | \
+    {n for n in SIGNATURES_BAG3D if n.endswith("_floats")}
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_int64, "f": ctypes.c_float,
        "d": ctypes.c_double, "s": ctypes.c_void_p}
@@ -233,7 +242,8 @@ def load():
                 "`python reconstruction-of-pde-without-time-label_amd/build.py` "
                 "(there is no CPU fallback)")
         lib = ctypes.CDLL(LIB_PATH)
-        for name, sig in {**SIGNATURES, **SIGNATURES_CONV3D, **SIGNATURES_FPE, **SIGNATURES_GPE2D}.items():
+        for name, sig in {**SIGNATURES, **SIGNATURES_CONV3D, **SIGNATURES_FPE, **SIGNATURES_GPE2D,
+                          **SIGNATURES_BAG3D}.items():
             fn = getattr(lib, name)
             fn.argtypes = [_CT[c] for c in sig]
             fn.restype = ctypes.c_int64 if name in RET64 else ctypes.c_int
@@ -245,7 +255,7 @@ def load():
 
 def exported_symbols():
     return (list(SIGNATURES) + list(SIGNATURES_CONV3D) + list(SIGNATURES_FPE) + list(SIGNATURES_GPE2D) +
-            ["blindno_error_string"])
+            list(SIGNATURES_BAG3D) + ["blindno_error_string"])
 
 
 def stream_ptr(device=None):

@@ -180,10 +180,14 @@ class FNO3d(nn.Module):
         self.fc1 = nn.Linear(self.width, 128)
         self.fc2 = nn.Linear(128, output_dim)
 
-    def forward(self, x):
+    def params(self):
+        """The parameter list ops.FNO3dFn (and ops.BagEncoder3dFn) take."""
         ps = [self.fc0.weight, self.fc0.bias]
         for k in range(ops.FNO3D_LAYERS):
             s, c = getattr(self, f"conv{k}"), getattr(self, f"w{k}")
             ps += [s.weights1, s.weights2, s.weights3, s.weights4, c.weight, c.bias]
         ps += [self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias]
-        return ops.FNO3dFn.apply(self.padding, x, *ps)
+        return ps
+
+    def forward(self, x):
+        return ops.FNO3dFn.apply(self.padding, x, *self.params())

@@ -1,5 +1,6 @@
 """Snapshot-bag (time-label-free) models: NIOFP2D_FNO, NIOFP_FNO, NIOFP2D, NIOFP,
-NIOFP_schrodinger, NIOFP3D -- drop-in for the reference's NIOModules.
+NIOFP_schrodinger, NIOFP3D -- drop-in for the reference's NIOModules -- and NIOFP3D_FNO, the
+project's own 3D FNO-NIO (the reference has no such class).
 
 Same constructor signatures, attribute names and initialisation order as
 2d_FPE/NIOModules.py:14-83,508-581, 2d_Non_conservative_FPE/NIOModules.py:13-82,503-577,
@@ -387,6 +388,61 @@ class NIOFP3D(nn.Module):
         h = ops.BagMeanFn.apply(ubar.view(B, 1, S), grid.reshape(S, 3), self.fc0.weight.data,
                                 self.fc0.bias.data, None)
         return self.fno(h.view(B, nx, ny, nz, -1))
+
+
+class NIOFP3D_FNO(nn.Module):
+    """3D FNO-NIO: the composite of NIOFP2D_FNO (2d_FPE/NIOModules.py:508-581) on three axes,
+    built from the reference's FNO3d (2d_FPE/FNOModules.py:290-366).  The reference has no such
+    class; this is the project's own, so there is no ``branch`` to keep a checkpoint layout for.
+
+    ``FNO_input`` = FNO3d(input_modes or modes, 4, 2, 4, 1) encodes every snapshot of the bag from
+    [u, gx, gy, gz]; ``fc0`` = Linear(4, width), read through ``.data`` and never trained, maps
+    [gx, gy, gz, bag mean] to the head's width (the bag-mean expression of NIOModules.py:565-575
+    with one more grid channel); ``fno`` = FNO3d(modes, width, fno_layers, width, output_dim) is
+    the single head (FNO3d.fc2 honours output_dim).  Train with
+    ``train.trained_parameters(model, exclude_prefixes=("fc0.",))``."""
+
+    accepts_dedup_bag = True    # forward(bag_idx=(unique idx, weights)): deduplicated bag
+
+    def __init__(self, fno_layers, width, modes, output_dim, device, input_modes=None):
+        super().__init__()
+        self.device = device
+        self.fno_layers = fno_layers
+        self.FNO_input = FNO3d(modes=input_modes or modes, width=4, n_layers=2, input_dim=4,
+                               output_dim=1, device=self.device)
+        self.fc0 = nn.Linear(4, width)
+        self.fno = FNO3d(modes=modes, width=width, n_layers=self.fno_layers, input_dim=width,
+                         output_dim=output_dim, device=self.device)
+
+    def forward(self, x, grid, bag_idx=None):
+        """x (B, T, Nx, Ny, Nz), grid (Nx, Ny, Nz, 3) -> (B, Nx, Ny, Nz, output_dim).  Train mode
+        draws the bag as the reference does (draw_bag: with replacement) and runs the encoder
+        once per distinct snapshot, weighted by multiplicity / L; eval mode uses all T snapshots;
+        ``bag_idx=`` overrides the draw.  The encoder, its projection and the bag mean are
+        ops.bag_encoder3d."""
+        ops.require_device(x, grid)
+        if x.dim() != 5 or tuple(grid.shape) != (*x.shape[2:], 3):
+            raise ValueError(f"NIOFP3D_FNO: expected x (B, T, Nx, Ny, Nz) and grid (Nx, Ny, Nz, 3), got "
+                             f"{tuple(x.shape)} and {tuple(grid.shape)}")
+        lw = None
+        if isinstance(bag_idx, tuple):
+            idx_t, lw = bag_idx                       # device-resident deduplicated bag
+        else:
+            if torch.is_tensor(bag_idx):
+                bag_idx = bag_idx.detach().cpu().numpy()
+            if bag_idx is not None:
+                idx = np.asarray(bag_idx)
+            elif self.training:
+                _, idx = draw_bag(x.shape[1])
+            else:
+                idx = np.arange(x.shape[1])
+            idx, w = dedup_bag(idx)
+            idx_t = torch.as_tensor(idx, device=x.device)
+            if w is not None:
+                lw = torch.as_tensor(w, device=x.device)
+        h = ops.bag_encoder3d(self.FNO_input.padding, x, idx_t, lw, grid, self.fc0.weight.data,
+                              self.fc0.bias.data, self.FNO_input.params())
+        return self.fno(h)
 
 
 class NIOFP(nn.Module):

@@ -1151,6 +1151,46 @@ def project3d_backward(z, fc1w, fc1b, fc2w, gout, N):
     return dz, gp[:o1].view(Hd, C), gp[o1:o2], gp[o2:o3].view(Cout, Hd), gp[o3:]
 
 
+def fno3d_layers_forward(x0, prm, sh: Spec3Shape):
+    """The four Fourier layers of FNO3d on the lifted field x0 (2d_FPE/FNOModules.py:341-358);
+    prm as FNO3dFn's.  Returns (saved spectra Xs, packed weights Wts, layer outputs zs)."""
+    Bn, C = sh.Bn, sh.Ci
+    src, act = x0, 0
+    Xs, Wts, zs = [], [], []
+    for k in range(FNO3D_LAYERS):
+        off = 2 + 6 * k
+        cw, cb = prm[off + 4], prm[off + 5]
+        Wt = k_pack_w3d(prm[off:off + 4], sh)
+        X, Z = spec3_forward(src, act, Wt, sh)
+        z = k_rowidft_epi(Z, src, cw, cb, Bn, C, sh.R, sh.P3, sh.m3, act)
+        Xs.append(X)
+        Wts.append(Wt)
+        zs.append(z)
+        src, act = z, 1
+    return Xs, Wts, zs
+
+
+def fno3d_layers_backward(dz, x0, Xs, Wts, zs, prm, sh: Spec3Shape, grads):
+    """Adjoint of fno3d_layers_forward from dz, the gradient of zs[-1] (the whole padded field):
+    fills the layers' entries of ``grads`` (indexed as prm) and returns the gradient of x0."""
+    Bn, C = sh.Bn, sh.Ci
+    for k in reversed(range(FNO3D_LAYERS)):
+        off = 2 + 6 * k
+        ws, cw = prm[off:off + 4], prm[off + 4]
+        src, act = (x0, 0) if k == 0 else (zs[k - 1], 1)
+        dWt, GZ = spec3_backward(dz, Xs[k], Wts[k], sh)
+        grads[off:off + 4] = k_unpack_w3d(dWt, ws, sh)
+        if C <= 4:
+            dz_new, gw, gb = k_rowidft_bwd(GZ, dz, cw, src, Bn, C, sh.R, sh.P3, sh.m3, act, True)
+        else:
+            gw, gb = k_conv_wgrad(dz, src, Bn, C, sh.R, sh.P3, act)
+            dz_new, _, _ = k_rowidft_bwd(GZ, dz, cw, src, Bn, C, sh.R, sh.P3, sh.m3, act)
+        grads[off + 4] = gw.view_as(cw)
+        grads[off + 5] = gb
+        dz = dz_new
+    return dz
+
+
 class FNO3dFn(torch.autograd.Function):
     """Whole FNO3d forward (2d_FPE/FNOModules.py:334-366) as one autograd node.
     prm = [fc0w, fc0b, (weights1..4, cw, cb) * 4, fc1w, fc1b, fc2w, fc2b]."""
@@ -1169,18 +1209,7 @@ class FNO3dFn(torch.autograd.Function):
         inp = _c(inp)
         prm = [_c(p) for p in prm]
         x0 = lift3d(inp, prm[0], prm[1], (P1, P2, P3))
-        src, act = x0, 0
-        Xs, Wts, zs = [], [], []
-        for k in range(n):
-            off = 2 + 6 * k
-            cw, cb = prm[off + 4], prm[off + 5]
-            Wt = k_pack_w3d(prm[off:off + 4], sh)
-            X, Z = spec3_forward(src, act, Wt, sh)
-            z = k_rowidft_epi(Z, src, cw, cb, Bn, C, sh.R, P3, m3, act)
-            Xs.append(X)
-            Wts.append(Wt)
-            zs.append(z)
-            src, act = z, 1
+        Xs, Wts, zs = fno3d_layers_forward(x0, prm, sh)
         fc1w, fc1b, fc2w, fc2b = prm[2 + 6 * n:]
         out = project3d(zs[-1].view(Bn, C, P1, P2, P3), fc1w, fc1b, fc2w, fc2b, (N1, N2, N3))
         ctx.sh, ctx.n = sh, n
@@ -1199,23 +1228,143 @@ class FNO3dFn(torch.autograd.Function):
         o = 2 + 6 * n
         dz, grads[o], grads[o + 1], grads[o + 2], grads[o + 3] = project3d_backward(
             zs[-1].view(Bn, C, *P), prm[o], prm[o + 1], prm[o + 2], _c(gout), tuple(inp.shape[1:4]))
-        for k in reversed(range(n)):
-            off = 2 + 6 * k
-            ws, cw = prm[off:off + 4], prm[off + 4]
-            src, act = (x0, 0) if k == 0 else (zs[k - 1], 1)
-            dWt, GZ = spec3_backward(dz, Xs[k], Wts[k], sh)
-            grads[off:off + 4] = k_unpack_w3d(dWt, ws, sh)
-            if C <= 4:
-                dz_new, gw, gb = k_rowidft_bwd(GZ, dz, cw, src, Bn, C, sh.R, sh.P3, sh.m3, act, True)
-            else:
-                gw, gb = k_conv_wgrad(dz, src, Bn, C, sh.R, sh.P3, act)
-                dz_new, _, _ = k_rowidft_bwd(GZ, dz, cw, src, Bn, C, sh.R, sh.P3, sh.m3, act)
-            grads[off + 4] = gw.view_as(cw)
-            grads[off + 5] = gb
-            dz = dz_new
+        dz = fno3d_layers_backward(dz, x0, Xs, Wts, zs, prm, sh, grads)
         d_inp, grads[0], grads[1] = lift3d_backward(dz, inp, prm[0], P, ctx.needs_input_grad[1])
         grads = [g if ctx.needs_input_grad[2 + i] else None for i, g in enumerate(grads)]
         return (None, d_inp, *grads)
+
+
+# ---------------------------------------------------------------------------- 3D bag encoder
+# NIOFP3D_FNO's snapshot encoder: FNO3d on every distinct snapshot of the bag, then the
+# fixed-weight bag mean.  The projection and the mean run at bag level (csrc/bagproj3d.hip),
+# as the 2D encoder's do: no per-snapshot output, and a backward that reduces 3 KiB of
+# statistics per (bag, point) instead of recomputing fc1 / GELU / GELU' per snapshot point.
+# False (tests, tools/bench_nio3d_fno.py): FNO3dFn on the snapshots + BagMeanFn, which other
+# shapes take anyway.
+BAG3D_STATS = True
+
+
+def _bag3d_stats_ok(B, U, C, P, N, Hd, Cout):
+    """The bag-level 3D projection applies: C <= 4, fc1 of 128, one output channel, U <= 1024,
+    32-bit offsets, statistics + v inside BAG_STATS_MAX_BYTES."""
+    if not (BAG3D_STATS and Hd == 128 and Cout == 1 and C <= 4 and U <= 1024):
+        return False
+    field = B * U * C * P[0] * P[1] * P[2]
+    if field >= 1 << 31:
+        return False
+    return 4 * (query("blindno_project_bag3d_stats_floats", B, *N) + field) <= BAG_STATS_MAX_BYTES
+
+
+def _bag3d_input(X, idx_t, grid):
+    """The encoder input of the bag's snapshots X[:, idx]: (B U, N1, N2, N3, 4) channels-last in
+    channel order [u, gx, gy, gz] (materialised; FNO3d's lift reads it)."""
+    B = X.shape[0]
+    U = idx_t.numel()
+    N = tuple(X.shape[2:])
+    u = X.index_select(1, idx_t.long()).reshape(B * U, *N, 1)
+    return torch.cat((u, grid.reshape(1, *N, 3).expand(B * U, *N, 3)), dim=-1)
+
+
+class BagEncoder3dFn(torch.autograd.Function):
+    """FNO3d snapshot encoder + bag-level projection + bag mean as one node: X (B, T, N1, N2, N3),
+    idx_t (U) the bag's distinct snapshots, lw (U) their multiplicity / L (None: 1 / U), grid
+    (N1, N2, N3, 3), (bw (width, 4), bb) the fixed fc0 in column order [gx, gy, gz, u]
+    (``.data``), prm as FNO3dFn's -> h (B, N1, N2, N3, width).  Gradients flow to prm only."""
+
+    @staticmethod
+    def forward(ctx, padding, X, idx_t, lw, grid, bw, bb, *prm):
+        require_device(X, idx_t, grid, bw, bb, *prm)
+        if X.dim() != 5 or tuple(grid.shape) != (*X.shape[2:], 3):
+            raise BlindnoError("BagEncoder3dFn takes X (B, T, N1, N2, N3) and grid (N1, N2, N3, 3)")
+        B, U = X.shape[0], idx_t.numel()
+        inp = _c(_bag3d_input(X, idx_t, grid))
+        Bn, N1, N2, N3, Cin, P1, P2, P3 = _fno3d_geometry(inp, padding)
+        n = FNO3D_LAYERS
+        if len(prm) != 2 + 6 * n + 4:
+            raise BlindnoError("FNO3d: bad parameter list")
+        C = prm[0].shape[0]
+        _check_w3d(prm[2:6], C)
+        m1, m2, m3 = prm[2].shape[2:]
+        fc1w, fc1b, fc2w, fc2b = prm[2 + 6 * n:]
+        P, N = (P1, P2, P3), (N1, N2, N3)
+        if not _bag3d_stats_ok(B, U, C, P, N, fc1w.shape[0], fc2w.shape[0]):
+            raise BlindnoError("BagEncoder3dFn: shape outside the bag-level projection "
+                               "(ops.bag_encoder3d takes the composition there)")
+        sh = Spec3Shape(Bn, C, C, P1, P2, P3, m1, m2, m3)
+        prm = [_c(p) for p in prm]
+        grid, bw, bb = _c(grid), _c(bw.detach()), _c(bb.detach())
+        lw = None if lw is None else _c(lw)
+        x0 = lift3d(inp, prm[0], prm[1], P)
+        Xs, Wts, zs = fno3d_layers_forward(x0, prm, sh)
+        S = N1 * N2 * N3
+        Hd = fc1w.shape[0]
+        ubar = _empty(B, S, like=inp)
+        stats = _empty(query("blindno_project_bag3d_stats_floats", B, *N), like=inp)
+        v = _empty(Bn, C, *P, like=inp)
+        call("blindno_project_bag3d_fwd", ptr(zs[-1]), ptr(fc1w), ptr(fc1b), ptr(fc2w), ptr(fc2b),
+             ptr(lw), ptr(ubar), ptr(stats), ptr(v), B, U, C, *P, *N, Hd, stream_ptr())
+        width = bw.shape[0]
+        h = _empty(B, S, width, like=inp)
+        one = torch.ones(1, dtype=F32, device=inp.device)
+        call("blindno_bagmean_fwd_w", ptr(ubar), ptr(grid), ptr(bw), ptr(bb), ptr(one), ptr(h), B, 1,
+             S, 3, width, stream_ptr())
+        ctx.sh, ctx.dims, ctx.lw = sh, (B, U, N, width), lw
+        # zs[-1] itself is not needed again: its statistics and v are
+        ctx.save_for_backward(inp, x0, stats, v, bw, *Xs, *Wts, *zs[:-1], *prm)
+        return h.view(B, N1, N2, N3, width)
+
+    @staticmethod
+    def backward(ctx, gh):
+        sh, n = ctx.sh, FNO3D_LAYERS
+        B, U, N, width = ctx.dims
+        t = ctx.saved_tensors
+        inp, x0, stats, v, bw = t[:5]
+        Xs, Wts, zs = t[5:5 + n], t[5 + n:5 + 2 * n], t[5 + 2 * n:4 + 3 * n]
+        prm = t[4 + 3 * n:]
+        Bn, C, P = sh.Bn, sh.Ci, (sh.P1, sh.P2, sh.P3)
+        S = N[0] * N[1] * N[2]
+        gh = _c(gh)
+        gs = _empty(B, S, like=gh)
+        call("blindno_bagmean_bwd", ptr(gh), ptr(bw), ptr(gs), B, S, 3, width, 1, stream_ptr())
+        grads: List[Optional[torch.Tensor]] = [None] * len(prm)
+        o = 2 + 6 * n
+        Hd = prm[o].shape[0]
+        np_p = Hd * C + 2 * Hd + 1
+        nchunk = query("blindno_project_bag3d_bwd_nchunk", B, *N)
+        partial = _empty(nchunk, np_p, like=gh)
+        dz = _empty(Bn, C, *P, like=gh)
+        call("blindno_project_bag3d_bwd", ptr(stats), ptr(gs), ptr(prm[o + 2]), ptr(ctx.lw), ptr(v),
+             ptr(dz), ptr(partial), nchunk, B, U, C, *P, *N, Hd, stream_ptr())
+        gp = reduce_partials(partial, nchunk, np_p)
+        o1, o2, o3 = Hd * C, Hd * C + Hd, Hd * C + 2 * Hd
+        grads[o], grads[o + 1] = gp[:o1].view(Hd, C), gp[o1:o2]
+        grads[o + 2], grads[o + 3] = gp[o2:o3].view(1, Hd), gp[o3:]
+        # the layer outputs but the last: fno3d_layers_backward reads zs[k - 1] only
+        dz = fno3d_layers_backward(dz, x0, Xs, Wts, list(zs) + [None], prm, sh, grads)
+        _, grads[0], grads[1] = lift3d_backward(dz, inp, prm[0], P, need_inp_grad=False)
+        grads = [g if ctx.needs_input_grad[7 + i] else None for i, g in enumerate(grads)]
+        ctx.lw = None
+        return (None, None, None, None, None, None, None, *grads)
+
+
+def bag_encoder3d(padding, X, idx_t, lw, grid, bw, bb, prm):
+    """h (B, N1, N2, N3, width) of NIOFP3D_FNO's encoder: BagEncoder3dFn where the bag-level
+    projection applies, otherwise (or with BAG3D_STATS off) FNO3dFn on the distinct snapshots
+    followed by BagMeanFn with lw -- same results."""
+    require_device(X, idx_t, grid, bw, bb, *prm)
+    B, U = X.shape[0], idx_t.numel()
+    N = tuple(X.shape[2:])
+    P = tuple(n + padding for n in N)
+    n = FNO3D_LAYERS
+    C, Hd, Cout = prm[0].shape[0], prm[2 + 6 * n].shape[0], prm[4 + 6 * n].shape[0]
+    if _bag3d_stats_ok(B, U, C, P, N, Hd, Cout):
+        return BagEncoder3dFn.apply(padding, X, idx_t, lw, grid, bw, bb, *prm)
+    u = FNO3dFn.apply(padding, _bag3d_input(X, idx_t, grid), *prm)      # (B U, N1, N2, N3, Cout)
+    if Cout != 1:
+        raise BlindnoError("the bag mean takes a one-channel snapshot encoder")
+    S = N[0] * N[1] * N[2]
+    h = BagMeanFn.apply(u.reshape(B, U, S), grid.reshape(S, 3), bw, bb, lw)
+    return h.view(B, *N, -1)
 
 
 # ---------------------------------------------------------------------------- grouped heads

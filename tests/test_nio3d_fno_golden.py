@@ -1,0 +1,196 @@
+"""NIOFP3D_FNO without a GPU: the float64 restatement (tests/nio3d_fno_ref.py) pinned to the golden
+run of the same composition in the reference's own fp32 code (tests/golden/nio3d_fno_train.npz,
+tests/golden/make_golden_nio3d_fno.py), the model's state_dict layout, the C ABI symbols of
+include/blindno_bag3d.h, and what must be rejected.
+
+Bars, those of tests/test_nio3d_golden.py (an fp32 reference measured against float64): out rel-L2
+<= 1e-4, every gradient rel-L2 <= 1e-3.  At capture time the fp32 reference sat at 5.9e-8 (out)
+and 1.4e-6 (worst gradient) against this restatement.
+"""
+import ctypes
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT, load_golden, rel_l2
+from recipe import make_array
+
+import nio3d_fno_ref
+
+NEW_SYMBOLS = ["blindno_project_bag3d_fwd", "blindno_project_bag3d_bwd",
+               "blindno_project_bag3d_stats_floats", "blindno_project_bag3d_bwd_nchunk"]
+CSRC = os.path.join(ROOT, "reconstruction-of-pde-without-time-label_amd", "csrc")
+
+
+def golden_state(g):
+    """(numpy state from the recipe, x) of the golden case."""
+    shapes = [(k, tuple(s)) for k, s in json.loads(str(g["layout_json"]))]
+    st = nio3d_fno_ref.make_state3d(shapes, int(g["recipe_seed"]), json.loads(str(g["complex_json"])))
+    x = make_array(tuple(int(v) for v in g["x_shape"]), int(g["recipe_seed"]), "nio3d_fno.x")
+    return st, x
+
+
+def golden_ctor(g):
+    return tuple(int(v) for v in g["ctor"])
+
+
+def check_grads(g, grad_of, bar):
+    """Every stored gradient of the golden against a {name: gradient tensor} lookup."""
+    n = 0
+    for k, v in g.items():
+        if k.startswith("g."):
+            got = grad_of(k[2:])
+            got = (torch.view_as_real(got) if got.is_complex() else got).detach().cpu().numpy()
+            e = rel_l2(got, v)
+            assert e <= bar, (k, e)
+            n += 1
+    assert n == 2 * (2 + 4 * 6 + 4)      # two FNO3d: fc0, four layers of 4 + 2, fc1, fc2
+    return n
+
+
+def test_ref_matches_reference_golden():
+    g = load_golden("nio3d_fno_train")
+    st, x = golden_state(g)
+    assert len(g["idx"]) == int(g["L"]) > len(set(g["idx"].tolist()))      # repeats in the bag
+    p = nio3d_fno_ref.leaves(st)
+    grid = torch.from_numpy(g["in.grid"]).double()
+    y = nio3d_fno_ref.niofp3d_fno(p, torch.from_numpy(x).double(), grid, idx=g["idx"].tolist())
+    e = rel_l2(y.detach().numpy(), g["out"])
+    print(f"nio3d_fno_train: fwd {e:.2e}")
+    assert e <= 1e-4, e
+    (y * torch.from_numpy(g["cot"]).double()).sum().backward()
+    check_grads(g, lambda k: p[k].grad, 1e-3)
+    assert p["fc0.weight"].grad is None and p["fc0.bias"].grad is None      # read through .data
+
+
+def test_golden_draw_is_draw_bag():
+    """The stored (L, idx) is what blindno.nio.draw_bag gives from the stored seed."""
+    import blindno
+    g = load_golden("nio3d_fno_train")
+    np.random.seed(int(g["bag_seed"]))
+    L, idx = blindno.draw_bag(int(g["x_shape"][1]))
+    assert L == int(g["L"]) and np.array_equal(idx, g["idx"])
+
+
+def test_state_dict_layout():
+    import blindno
+    m = blindno.NIOFP3D_FNO(2, 6, 3, 2, "cpu", input_modes=2)
+    sd = m.state_dict()
+    assert {k.split(".")[0] for k in sd} == {"FNO_input", "fc0", "fno"}
+    assert list(sd)[0].startswith("FNO_input.") and list(sd)[-1].startswith("fno.")
+    assert tuple(sd["fc0.weight"].shape) == (6, 4) and tuple(sd["fc0.bias"].shape) == (6,)
+    for pre, C, m_ in (("FNO_input", 4, 2), ("fno", 6, 3)):
+        assert tuple(sd[f"{pre}.fc0.weight"].shape) == (C, 4 if pre == "FNO_input" else 6)
+        for k in range(4):
+            for q in range(1, 5):
+                w = sd[f"{pre}.conv{k}.weights{q}"]
+                assert w.dtype == torch.complex64 and tuple(w.shape) == (C, C, m_, m_, m_)
+            assert tuple(sd[f"{pre}.w{k}.weight"].shape) == (C, C, 1, 1, 1)
+        assert tuple(sd[f"{pre}.fc1.weight"].shape) == (128, C)
+    assert tuple(sd["FNO_input.fc2.weight"].shape) == (1, 128)
+    assert tuple(sd["fno.fc2.weight"].shape) == (2, 128)         # one head, output_dim channels
+    assert not hasattr(m, "branch")
+    # input_modes defaults to modes
+    assert tuple(blindno.NIOFP3D_FNO(2, 6, 3, 2, "cpu").state_dict()["FNO_input.conv0.weights1"].shape) == (4, 4, 3, 3, 3)
+
+
+def test_golden_layout_is_the_model_layout():
+    """The recipe layout stored with the golden (the composition of the reference's classes at
+    capture time) is NIOFP3D_FNO's: its parameters load with strict=True."""
+    import blindno
+    from blindno.train import trained_parameters
+    g = load_golden("nio3d_fno_train")
+    st, _ = golden_state(g)
+    m = blindno.NIOFP3D_FNO(*golden_ctor(g), "cpu")
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()}, strict=True)
+    names = {id(p): k for k, p in m.named_parameters()}
+    trained = [names[id(p)] for p in trained_parameters(m, exclude_prefixes=("fc0.",))]
+    assert sorted("g." + k for k in trained) == sorted(k for k in g if k.startswith("g."))
+
+
+def test_new_symbols_declared_and_bound():
+    """include/blindno_bag3d.h (included by blindno.h) <=> _lib.SIGNATURES_BAG3D <=> the library."""
+    import blindno
+    from blindno import _lib
+    assert '#include "blindno_bag3d.h"' in open(os.path.join(ROOT, "include", "blindno.h")).read()
+    hdr = open(os.path.join(ROOT, "include", "blindno_bag3d.h")).read()
+    decl = sorted(set(re.findall(r"^(?:int|int64_t|const char\*)\s+(blindno_\w+)\(", hdr, re.M)))
+    assert decl == sorted(NEW_SYMBOLS) == sorted(_lib.SIGNATURES_BAG3D)
+    others = (set(_lib.SIGNATURES) | set(_lib.SIGNATURES_CONV3D) | set(_lib.SIGNATURES_FPE) |
+              set(_lib.SIGNATURES_GPE2D))
+    assert not set(_lib.SIGNATURES_BAG3D) & others
+    lib = blindno.load_library()
+    for s in NEW_SYMBOLS:
+        assert hasattr(lib, s) and s in _lib.exported_symbols(), s
+        m = re.search(r"\b(?:int|int64_t)\s+" + s + r"\s*\(([^;]*)\)\s*;", hdr)
+        assert m, s
+        nargs = len([a for a in m.group(1).split(",") if a.strip()])
+        assert nargs == len(_lib.SIGNATURES_BAG3D[s]) == len(getattr(lib, s).argtypes), (s, nargs)
+    assert lib.blindno_project_bag3d_stats_floats.restype is ctypes.c_int64
+    # host-only size queries work without a device: 3 KiB of statistics per point, in 16-point tiles
+    assert _lib.query("blindno_project_bag3d_stats_floats", 2, 7, 6, 5) == (420 + 15) // 16 * 16 * 768
+    assert _lib.query("blindno_project_bag3d_stats_floats", 4, 40, 40, 40) * 4 == 4 * 40 ** 3 * 3072
+    assert 1 <= _lib.query("blindno_project_bag3d_bwd_nchunk", 2, 7, 6, 5) <= 27
+    assert 1 <= _lib.query("blindno_project_bag3d_bwd_nchunk", 4, 40, 40, 40) <= 1024
+
+
+def test_no_atomics_in_the_kernel_source():
+    for name in ("bagproj3d.hip", "bagproj.h"):
+        assert "atomic" not in open(os.path.join(CSRC, name)).read().lower(), name
+
+
+def _rc(lib, name, dims):
+    """The entry called with non-NULL placeholder pointers: only reached when it refuses."""
+    npt = len(blindno_sig(name)) - len(dims) - 1
+    if name.endswith("_bwd"):                       # ... partial, nchunk, dims
+        args = [ctypes.c_void_p(64)] * (npt - 1) + [1] + list(dims)
+    else:
+        args = [ctypes.c_void_p(64)] * npt + list(dims)
+    return getattr(lib, name)(*args, None)
+
+
+def blindno_sig(name):
+    from blindno import _lib
+    return _lib.SIGNATURES_BAG3D[name]
+
+
+@pytest.mark.parametrize("name", ["blindno_project_bag3d_fwd", "blindno_project_bag3d_bwd"])
+def test_refuses_fields_past_2_31(name):
+    """B U C P1 P2 P3 >= 2^31 (32-bit offsets), and the other limits of the contract, return
+    hipErrorInvalidValue before anything is launched -- on a machine with no device, too."""
+    import blindno
+    lib = blindno.load_library()
+    INVALID = 1                                     # hipErrorInvalidValue
+    #        B  U    C  P1   P2   P3   N1   N2   N3   Hd
+    assert _rc(lib, name, (4, 128, 4, 128, 128, 64, 126, 126, 62, 128)) == INVALID     # = 2^31
+    assert _rc(lib, name, (8, 1024, 4, 512, 512, 512, 510, 510, 510, 128)) == INVALID  # = 2^42
+    assert _rc(lib, name, (2, 1025, 4, 9, 8, 7, 7, 6, 5, 128)) == INVALID      # U > 1024
+    assert _rc(lib, name, (2, 8, 5, 9, 8, 7, 7, 6, 5, 128)) == INVALID         # C > 4
+    assert _rc(lib, name, (2, 8, 4, 9, 8, 7, 7, 6, 5, 64)) == INVALID          # Hd != 128
+    assert _rc(lib, name, (2, 8, 4, 9, 8, 7, 7, 9, 5, 128)) == INVALID         # N2 > P2
+
+
+def test_cpu_tensors_are_rejected():
+    import blindno
+    from blindno import ops
+    m = blindno.NIOFP3D_FNO(2, 4, 2, 2, "cpu")
+    with pytest.raises(blindno.BlindnoError):
+        m(torch.zeros(1, 60, 7, 6, 5), torch.zeros(7, 6, 5, 3))
+    with pytest.raises(blindno.BlindnoError):
+        ops.BagEncoder3dFn.apply(2, torch.zeros(1, 60, 7, 6, 5), torch.arange(3), None,
+                                 torch.zeros(7, 6, 5, 3), m.fc0.weight.data, m.fc0.bias.data,
+                                 *m.FNO_input.params())
+
+
+def test_absent_from_the_dropin_namespaces():
+    """The class is the project's own: the reference's NIOModules never defines it."""
+    import blindno
+    from blindno import dropin
+    assert blindno.NIOFP3D_FNO is blindno.nio.NIOFP3D_FNO
+    for exp in dropin.EXPERIMENTS:
+        for mod in ("NIOModules", "FNOModules"):
+            assert not hasattr(dropin.module(exp, mod), "NIOFP3D_FNO"), (exp, mod)

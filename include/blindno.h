@@ -894,5 +894,6 @@ int blindno_project3d_bwd(const float* z, const float* w1, const float* b1, cons
 #include "blindno_fpe.h"
 #include "blindno_gpe2d.h"
 #include "blindno_bag3d.h"
+#include "blindno_gpe3d.h"
 
 #endif /* BLINDNO_H */

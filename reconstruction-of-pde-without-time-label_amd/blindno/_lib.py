@@ -213,8 +213,18 @@ SIGNATURES_BAG3D = {
     "blindno_project_bag3d_bwd": "ppppppp" + "i" + "iiiiiiiiii" + "s",
 }
 
+# include/blindno_gpe3d.h: the grid-resident 3D GPE solver and the 3D trapezoid residual
+# (csrc/gpe3d.hip)
+SIGNATURES_GPE3D = {
+    "blindno_gpe3d_scratch_doubles": "iiii",
+    "blindno_gpe3d_launches": "ii",
+    "blindno_gpe3d_solve": "pppp" + "dddd" + "iii" + "pipp" + "p" + "iiiii" + "s",
+    "blindno_trapz3_frames": "pppppp" + "iiii" + "s",
+}
+
 # entry points returning int64_t (byte counts) instead of an error code / int count
 RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))} | \
+    {n for n in SIGNATURES_GPE3D if n.endswith(("_doubles", "_launches"))} | \
     {n for n in SIGNATURES_FPE if n.endswith("_doubles")} | \
     {n for n in SIGNATURES_GPE2D if n.endswith(("_doubles", "_launches"))} | \
     {n for n in SIGNATURES_BAG3D if n.endswith("_floats")}
@@ -243,7 +253,7 @@ def load():
                 "(there is no CPU fallback)")
         lib = ctypes.CDLL(LIB_PATH)
         for name, sig in {**SIGNATURES, **SIGNATURES_CONV3D, **SIGNATURES_FPE, **SIGNATURES_GPE2D,
-                          **SIGNATURES_BAG3D}.items():
+                          **SIGNATURES_BAG3D, **SIGNATURES_GPE3D}.items():
             fn = getattr(lib, name)
             fn.argtypes = [_CT[c] for c in sig]
             fn.restype = ctypes.c_int64 if name in RET64 else ctypes.c_int
@@ -255,7 +265,7 @@ def load():
 
 def exported_symbols():
     return (list(SIGNATURES) + list(SIGNATURES_CONV3D) + list(SIGNATURES_FPE) + list(SIGNATURES_GPE2D) +
-            list(SIGNATURES_BAG3D) + ["blindno_error_string"])
+            list(SIGNATURES_BAG3D) + list(SIGNATURES_GPE3D) + ["blindno_error_string"])
 
 
 def stream_ptr(device=None):

@@ -1,6 +1,7 @@
 """Gross-Pitaevskii data generators / density propagators and the density-error metrics on the
 GPU, fp64 like the reference: 1D (libblindno ``blindno_gpe_solve`` / ``blindno_trapz_rows``) and
-2D (``blindno_gpe2d_solve`` / ``blindno_trapz2_frames``, the ``*_2d`` functions at the end).
+2D (``blindno_gpe2d_solve`` / ``blindno_trapz2_frames``, the ``*_2d`` functions) and 3D
+(``blindno_gpe3d_solve`` / ``blindno_trapz3_frames``, the ``*_3d`` functions at the end).
 
 Reference (yl602019618/Reconstruction-of-PDE-without-Time-Label):
   get_initial_condition, solve_GPE_custom, generate_and_save_training_data
@@ -329,6 +330,183 @@ def time_averaged_L2_error_2d(time_ref, rho_ref, time_pred, rho_pred, grid, eps:
     a, b = d64(rho_pred), d64(rho_ref)
     s = torch.empty(nt, 2, dtype=F64, device=dev)
     call("blindno_trapz2_frames", ptr(a), ptr(b), ptr(d64(xg)), ptr(d64(yg)), ptr(s), nt, nx, ny, stream_ptr(dev))
+    rel = s[:, 0].clamp_min(0).sqrt() / (s[:, 1].clamp_min(0).sqrt() + eps)
+    t = d64(time_ref)
+    integral = (0.5 * (rel[:-1] + rel[1:]) * (t[1:] - t[:-1])).sum()
+    return float(integral / (t[-1] - t[0]))
+
+
+# ------------------------------------------------------------------------------------- 3D
+# The project's own, like the 2D functions above: the same scheme on three axes (csrc/gpe3d.hip,
+# grid-resident; every kinetic step is a z launch, a y launch and an x launch).
+
+# The launches one solve_batch_3d call may enqueue (3 per Strang step, 12 per Yoshida step).  The
+# rule of MAX_LAUNCHES_2D: the largest power of two whose worst case stays under 120 s at the time
+# per launch measured by tools/bench_gpe3d.py at its headline shape, 64^3 with B = 16
+# (profiles/gpe3d_bench.json: 77.39 us per launch; 120 s / 77.39 us = 1.55 M, 2^20 launches take
+# 81.1 s and 2^21 would take 162.3 s).
+MAX_LAUNCHES_3D = 1 << 20
+
+
+def solve_batch_3d(psi0, x, y, z, dt: float, t_final: float, order: int, g, kappa, V,
+                   rec_every: int = 1, want_abs: bool = True, want_psi: bool = False,
+                   abs_dtype=torch.float64, device=None):
+    """``solve_batch_2d`` on a periodic 3D grid: integrate B trajectories at once.
+
+    psi0: (Nx, Ny, Nz) or (B, Nx, Ny, Nz) complex initial field; V: (Nx, Ny, Nz) or
+    (B, Nx, Ny, Nz); g, kappa: scalars or (B,); x (Nx), y (Ny), z (Nz) uniform grids, each a power
+    of two in [4, 1024] points with Nx Ny Nz <= 2^24.  Returns a dict with ``t`` (numpy, the
+    recorded times), ``abs`` (B, nrec, Nx, Ny, Nz) device tensor of |psi| in ``abs_dtype`` (fp64,
+    or fp32 = the fp64 value rounded on the device; if ``want_abs``), ``psi``
+    (B, nrec, Nx, Ny, Nz) complex128 (if ``want_psi``) and ``final`` (B, Nx, Ny, Nz) complex128.
+    Records every ``rec_every``-th step, step 0 included.
+
+    Refused before anything is launched (BlindnoError): a request of more than MAX_LAUNCHES_3D
+    kernel launches, a record above MAX_RECORD_BYTES, and whatever blindno_gpe3d_solve refuses."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    z = np.asarray(z, dtype=np.float64)
+    shape = (len(x), len(y), len(z))
+    nx, ny, nz = shape
+    V = np.asarray(V, dtype=np.float64)
+    if V.ndim == 3:
+        V = V[None]
+    if V.ndim != 4 or V.shape[1:] != shape:
+        raise BlindnoError(f"V has shape {V.shape}; expected (B, {nx}, {ny}, {nz}) or ({nx}, {ny}, {nz})")
+    B = V.shape[0]
+    psi0 = np.asarray(psi0, dtype=np.complex128)
+    batched = psi0.ndim == 4
+    if psi0.shape[-3:] != shape or psi0.ndim not in (3, 4):
+        raise BlindnoError(f"psi0 has shape {psi0.shape}; expected (B, {nx}, {ny}, {nz}) or ({nx}, {ny}, {nz})")
+    if batched and psi0.shape[0] != B:
+        raise BlindnoError("psi0 and V batch sizes differ")
+    g = np.broadcast_to(np.asarray(g, dtype=np.float64), (B,)).copy()
+    kappa = np.broadcast_to(np.asarray(kappa, dtype=np.float64), (B,)).copy()
+    for name, n in (("Nx", nx), ("Ny", ny), ("Nz", nz)):
+        if n & (n - 1) or n < 4 or n > 1024:
+            raise BlindnoError(f"{name} = {n}: the 3D solver needs a power of two in [4, 1024]")
+    if nx * ny * nz > 1 << 24:
+        raise BlindnoError(f"{nx} x {ny} x {nz} cells: the 3D solver takes at most 2^24 per trajectory")
+    if order not in (2, 4):
+        raise BlindnoError(f"order = {order}: the solver has orders 2 and 4")
+    if int(rec_every) < 1:
+        raise BlindnoError(f"rec_every = {rec_every}: must be at least 1")
+    if abs_dtype not in (torch.float64, torch.float32):
+        raise BlindnoError(f"abs_dtype = {abs_dtype}: |psi| is recorded in float64 or float32")
+    nt = int(t_final / dt) + 1
+    nsteps = nt - 1
+    nrec = nsteps // int(rec_every) + 1
+    launches = query("blindno_gpe3d_launches", nsteps, int(order))
+    if launches > MAX_LAUNCHES_3D:
+        raise BlindnoError(
+            f"{nsteps} steps of order {order} are {launches} kernel launches (limit MAX_LAUNCHES_3D = "
+            f"{MAX_LAUNCHES_3D}); refusing to launch -- integrate in several calls, continuing from 'final'")
+    abs_bytes = 8 if abs_dtype == torch.float64 else 4
+    rec_bytes = B * nrec * nx * ny * nz * ((abs_bytes if want_abs else 0) + (16 if want_psi else 0))
+    if rec_bytes > MAX_RECORD_BYTES:
+        raise BlindnoError(
+            f"the record of {B} trajectories x {nrec} frames x {nx} x {ny} x {nz} is {rec_bytes} bytes (limit "
+            f"MAX_RECORD_BYTES = {MAX_RECORD_BYTES}); refusing to launch -- raise rec_every, record float32 "
+            f"|psi| or solve fewer trajectories per call")
+    dev = _dev(device)
+    t_full = np.linspace(0, t_final, nt)
+    # fresh C-ordered copies: the inputs may be read-only or broadcast views
+    p0 = torch.from_numpy(np.array(psi0, order="C").view(np.float64)).to(dev)
+    Vd = torch.from_numpy(np.array(V, order="C")).to(dev)
+    gd = torch.from_numpy(g).to(dev)
+    kd = torch.from_numpy(kappa).to(dev)
+    rabs = torch.empty(B, nrec, nx, ny, nz, dtype=abs_dtype, device=dev) if want_abs else None
+    rpsi = torch.empty(B, nrec, nx, ny, nz, 2, dtype=F64, device=dev) if want_psi else None
+    fin = torch.empty(B, nx, ny, nz, 2, dtype=F64, device=dev)
+    scratch = torch.empty(query("blindno_gpe3d_scratch_doubles", B, nx, ny, nz), dtype=F64, device=dev)
+    call("blindno_gpe3d_solve", ptr(p0), ptr(Vd), ptr(gd), ptr(kd), float(x[1] - x[0]), float(y[1] - y[0]),
+         float(z[1] - z[0]), float(dt), nsteps, int(order), int(rec_every), ptr(rabs),
+         int(abs_dtype == torch.float32), ptr(rpsi), ptr(fin), ptr(scratch), B, nx, ny, nz, int(batched),
+         stream_ptr(dev))
+    out = {"t": t_full[::rec_every][:nrec], "final": torch.view_as_complex(fin)}
+    if want_abs:
+        out["abs"] = rabs
+    if want_psi:
+        out["psi"] = torch.view_as_complex(rpsi)
+    return out
+
+
+def training_potentials_3d(num_orbits: int, x: np.ndarray, y: np.ndarray, z: np.ndarray,
+                           rng=np.random) -> np.ndarray:
+    """The random draws of ``generate_training_data_3d``, per orbit in this order: a ~ U(0.1, 0.3),
+    b ~ U(0.5, 2), c ~ U(0.5, 2), x0, y0, z0 ~ U(-3, 3) ->
+    V = a ((x - x0)^2 + (y - y0)^2 + (z - z0)^2) + b cos^2(c (x - x0)) cos^2(c (y - y0)) cos^2(c (z - z0)),
+    (M, Nx, Ny, Nz)."""
+    X, Y, Z = x[:, None, None], y[None, :, None], z[None, None, :]
+    Vs = []
+    for _ in range(num_orbits):
+        a = rng.uniform(0.1, 0.3)
+        b = rng.uniform(0.5, 2)
+        c = rng.uniform(0.5, 2)
+        x0 = rng.uniform(-3, 3)
+        y0 = rng.uniform(-3, 3)
+        z0 = rng.uniform(-3, 3)
+        Vs.append(a * ((X - x0) ** 2 + (Y - y0) ** 2 + (Z - z0) ** 2) +
+                  b * np.cos(c * (X - x0)) ** 2 * np.cos(c * (Y - y0)) ** 2 * np.cos(c * (Z - z0)) ** 2)
+    return np.stack(Vs, 0)
+
+
+def generate_training_data_3d(num_orbits: int, Nx: int = 64, Ny: int = 64, Nz: int = 64, dt: float = 0.005,
+                              t_final: float = 5.0, order: int = 2, rng=np.random, device=None,
+                              batch: int = 16, y_dtype=np.float32):
+    """The 3D GPE training set (the project's own generator).  Per orbit the draws of
+    ``training_potentials_3d`` on [-10, 10]^3, psi0 = ic2(x) ic2(y) ic2(z), g = kappa = 2,
+    y = |psi|[::10].  Returns the 1D generator's dict {'y': (M, Nt//10 + 1, Nx, Ny, Nz), 'g',
+    'kappa', 'V'}, so ``save_training_data`` and ``data.ParameterDataset`` take it unchanged.
+
+    ``y`` is float32 by default, as in 2D (``y_dtype=np.float64`` for the full record): the cast
+    happens on the device and is the fp64 value rounded once.  The default ``batch`` keeps one
+    call's record under MAX_RECORD_BYTES at the defaults even in fp64: 16 orbits x 101 frames x
+    64^3 points x 8 B = 3.4 GB of the 8 GiB."""
+    if np.dtype(y_dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("y_dtype must be float32 or float64")
+    x = np.linspace(-10, 10, Nx)
+    y = np.linspace(-10, 10, Ny)
+    z = np.linspace(-10, 10, Nz)
+    V = training_potentials_3d(num_orbits, x, y, z, rng)
+    psi0 = (initial_condition(2, x)[:, None, None] * initial_condition(2, y)[None, :, None] *
+            initial_condition(2, z)[None, None, :])
+    tdt = torch.float32 if np.dtype(y_dtype) == np.dtype(np.float32) else torch.float64
+    ys = []
+    for s in range(0, num_orbits, batch):
+        r = solve_batch_3d(psi0, x, y, z, dt, t_final, order, 2.0, 2.0, V[s:s + batch], rec_every=10,
+                           abs_dtype=tdt, device=device)
+        ys.append(r["abs"].cpu().numpy())
+    return {"y": np.concatenate(ys, 0), "g": np.full(num_orbits, 2), "kappa": np.full(num_orbits, 2), "V": V}
+
+
+def time_averaged_L2_error_3d(time_ref, rho_ref, time_pred, rho_pred, grid, eps: float = 1e-12,
+                              device=None) -> float:
+    """``time_averaged_L2_error_2d`` for (Nt, Nx, Ny, Nz) densities on ``grid = (x, y, z)``: per
+    time sqrt(trapz_z(trapz_y(trapz_x((rho_pred - rho_ref)^2)))) / (sqrt(the same of rho_ref^2) +
+    eps), then the trapezoid time average / (t_end - t_0).  rho_* are numpy arrays or device
+    tensors; the spatial integrals run on the GPU in fp64 (blindno_trapz3_frames)."""
+    dev = _dev(device if device is not None else (rho_ref.device if torch.is_tensor(rho_ref) else None))
+    if tuple(rho_ref.shape) != tuple(rho_pred.shape) or len(rho_ref.shape) != 4:
+        raise ValueError(f"rho_ref shape {tuple(rho_ref.shape)} / rho_pred shape {tuple(rho_pred.shape)}: "
+                         "expected two equal (Nt, Nx, Ny, Nz) arrays")
+    if not isinstance(grid, (list, tuple)) or len(grid) != 3:
+        raise ValueError("grid must be (x, y, z)")
+    xg, yg, zg = (np.asarray(a, dtype=np.float64).reshape(-1) for a in grid)
+    nt, nx, ny, nz = (int(v) for v in rho_ref.shape)
+    if (len(xg), len(yg), len(zg)) != (nx, ny, nz):
+        raise ValueError(f"grid sizes {(len(xg), len(yg), len(zg))} do not match the frames {(nx, ny, nz)}")
+    if not np.allclose(np.asarray(time_ref), np.asarray(time_pred)):
+        raise ValueError("time_ref and time_pred differ")
+
+    def d64(a):
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a))
+        return t.to(dev, F64).contiguous()
+
+    a, b = d64(rho_pred), d64(rho_ref)
+    s = torch.empty(nt, 2, dtype=F64, device=dev)
+    call("blindno_trapz3_frames", ptr(a), ptr(b), ptr(d64(xg)), ptr(d64(yg)), ptr(d64(zg)), ptr(s), nt, nx, ny, nz,
+         stream_ptr(dev))
     rel = s[:, 0].clamp_min(0).sqrt() / (s[:, 1].clamp_min(0).sqrt() + eps)
     t = d64(time_ref)
     integral = (0.5 * (rel[:-1] + rel[1:]) * (t[1:] - t[:-1])).sum()

@@ -2,7 +2,8 @@
 compute_time_error.py:361-510 (``compute_time_error``, FPE forces), 1d_FPE/
 compute_time_error.py:215-420 (``compute_time_error_1d``, potential + drag) and 1d_GPE/
 compute_time_error_GPE.py:208-330 (``compute_time_error_gpe``, GPE potentials; its 2D
-counterpart ``compute_time_error_gpe_2d`` is the project's own), each as one batched pipeline.
+and 3D counterparts ``compute_time_error_gpe_2d`` / ``_3d`` are the project's own), each as one
+batched pipeline.
 
 Per test index the reference normalises the bag with the train statistics, predicts (Fx, Fy)
 with each model, de-normalises, propagates a Gaussian density (centre (-150, -150) nm, width
@@ -212,6 +213,96 @@ def compute_time_error_gpe_2d(models: Dict[str, torch.nn.Module], train, test, i
                 np.save(os.path.join(d, f"sample_{i}_V_and_err.npy"),
                         {"x": x, "y": y, "true_V": V[k * per], "pred_V": V[k * per + 1 + j], "g": g[k * per],
                          "kappa": kappa[k * per], "Err_L2_rel": e})
+    out = {name: np.array(v, dtype=float) for name, v in errs.items()}
+    if outdir is not None:
+        for name, arr in out.items():
+            np.save(os.path.join(outdir, f"ErrL2_relative_{name}_Nsamples_{len(idx)}.npy"), arr)
+    return out
+
+
+# ------------------------------------------------------------------------------- 3D GPE
+def grid3d(nx: int, ny: int, nz: int, device) -> torch.Tensor:
+    """The (Nx, Ny, Nz, 3) grid on [-1, 1]^3 the 3D models read (evaluate.grid2d with one more axis)."""
+    g = np.meshgrid(*(np.linspace(-1, 1, n, dtype=np.float32) for n in (nx, ny, nz)), indexing="ij")
+    return torch.tensor(np.stack(g, axis=3), device=device)
+
+
+def compute_time_error_gpe_3d(models: Dict[str, torch.nn.Module], train, test, indices: Iterable[int],
+                              outdir: Optional[str] = None, order: int = 2, dt: float = 0.005,
+                              t_final: float = 5.0, init_ic: int = 2, batch: int = 2, rec_every: int = 10,
+                              device="cuda") -> Dict[str, np.ndarray]:
+    """``compute_time_error_gpe_2d`` with the 3D solver and error (``train`` / ``test`` are
+    blindno.gpe.generate_training_data_3d dicts; the models map x (B, T, Nx, Ny, Nz) and a
+    (Nx, Ny, Nz, 3) grid to V, e.g. NIOFP3D_FNO(..., output_dim=1)): per test index, V predicted by
+    each model (de-normalised with the train V_max), |psi| propagated from psi0 = ic(x) ic(y) ic(z)
+    on [-10, 10]^3 under the true V and under each prediction (true g, kappa), and
+    time_averaged_L2_error_3d of the densities.  All trajectories -- reference and every model's,
+    for every index -- go into blindno.gpe.solve_batch_3d calls, each of as many trajectories (whole
+    indices where one fits) as keep its fp64 |psi| record, every ``rec_every``-th step, under
+    gpe.MAX_RECORD_BYTES; the solver is independent of the batch bit for bit, so the chunking does
+    not change a digit.  Returns {model: errors in index order}; with ``outdir`` writes
+    <outdir>/<model>/sample_<idx>_V_and_err.npy and ErrL2_relative_<model>_Nsamples_<n>.npy as the
+    2D function does (x, y and z in the dict)."""
+    from . import gpe
+    sc = evaluate.compute_train_scalers_gpe(train)
+    tn = evaluate.normalize_gpe(test, sc)
+    yy = np.asarray(tn["y"])
+    idx = [int(i) for i in indices if 0 <= int(i) < yy.shape[0]]
+    if not idx:
+        return {name: np.zeros(0) for name in models}
+    nx, ny, nz = yy.shape[2:5]
+    xin = torch.tensor(np.stack([yy[i] for i in idx]), dtype=torch.float32, device=device)
+    grid_n = grid3d(nx, ny, nz, device)
+    preds = {}
+    for name, m in models.items():
+        p = evaluate.predict(m, xin, grid_n, batch).cpu().numpy()
+        preds[name] = (p[..., 0] if p.ndim == 5 else p) * sc["V_max"]
+    x, y, z = (np.linspace(-10, 10, n) for n in (nx, ny, nz))
+    V, g, kappa = [], [], []
+    for k, i in enumerate(idx):
+        gi = float(np.atleast_1d(test["g"][i])[0])
+        ki = float(np.atleast_1d(test["kappa"][i])[0])
+        for Vi in [tn["V"][i] * sc["V_max"]] + [preds[name][k] for name in models]:
+            V.append(Vi)
+            g.append(gi)
+            kappa.append(ki)
+    psi0 = (gpe.initial_condition(init_ic, x)[:, None, None] * gpe.initial_condition(init_ic, y)[None, :, None] *
+            gpe.initial_condition(init_ic, z)[None, None, :])
+    per = 1 + len(models)
+    nrec = (int(t_final / dt)) // int(rec_every) + 1
+    traj_bytes = nrec * nx * ny * nz * 8
+    fit = int(gpe.MAX_RECORD_BYTES // traj_bytes)             # trajectories per call
+    if fit < 1:
+        raise gpe.BlindnoError(
+            f"one trajectory's record ({traj_bytes} bytes) is above MAX_RECORD_BYTES = {gpe.MAX_RECORD_BYTES}; "
+            "raise rec_every")
+    chunk = fit // per * per if fit >= per else fit           # whole indices where one fits
+    errs = {name: [] for name in models}
+    t, rho, base = None, None, 0
+
+    def traj(n):
+        """|psi| record of trajectory n: its chunk is solved when first needed, one chunk resident."""
+        nonlocal t, rho, base
+        if rho is None or not base <= n < base + rho.shape[0]:
+            rho = None                                        # free the previous chunk first
+            base = n // chunk * chunk
+            s = slice(base, base + chunk)
+            r = gpe.solve_batch_3d(psi0, x, y, z, dt, t_final, order, np.array(g[s]), np.array(kappa[s]),
+                                   np.array(V[s]), rec_every=rec_every, device=device)
+            t, rho = r["t"], r["abs"]
+        return rho[n - base]
+
+    for k, i in enumerate(idx):
+        ref = traj(k * per).clone() if chunk % per else traj(k * per)
+        for j, name in enumerate(models):
+            e = gpe.time_averaged_L2_error_3d(t, ref, t, traj(k * per + 1 + j), (x, y, z))
+            errs[name].append(e)
+            if outdir is not None:
+                d = os.path.join(outdir, name)
+                os.makedirs(d, exist_ok=True)
+                np.save(os.path.join(d, f"sample_{i}_V_and_err.npy"),
+                        {"x": x, "y": y, "z": z, "true_V": V[k * per], "pred_V": V[k * per + 1 + j],
+                         "g": g[k * per], "kappa": kappa[k * per], "Err_L2_rel": e})
     out = {name: np.array(v, dtype=float) for name, v in errs.items()}
     if outdir is not None:
         for name, arr in out.items():

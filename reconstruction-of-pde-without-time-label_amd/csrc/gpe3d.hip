@@ -1,0 +1,461 @@
+// Grid-resident 3D Gross-Pitaevskii split-step solver and the 3D trapezoid density residual
+// (include/blindno_gpe3d.h).
+//
+//   i psi_t = -1/2 (psi_xx + psi_yy + psi_zz) + (V + g |psi|^2 + kappa |psi|^4) psi
+// on a periodic nx x ny x nz grid (row-major, z contiguous, complex128 interleaved): the 2D
+// integrator of csrc/gpe2d.hip with one more axis.
+//   N(h): psi <- exp(-i h (V + g|psi|^2 + kappa|psi|^4)) psi                     pointwise
+//   L(h): psi <- ifftn(exp(-i h/2 (kx^2 + ky^2 + kz^2)) fftn psi)                 k = 2 pi fftfreq
+// Strang N(dt/2) L(dt) N(dt/2) or the nine-stage Yoshida sequence per step.
+//
+// The kinetic phase factorises, so L = L_x L_y L_z and each factor is a batch of independent 1D
+// transforms (FFT, multiply, inverse FFT, 1/n) along one axis.  All three are one kernel
+// template, the tile scheme of gpe2d.hip's row and column passes:
+//   z pass  (ROW layout) a workgroup owns `tile` whole z-lines, a contiguous chunk of the field;
+//   y pass  (COL layout) for one ix, a workgroup owns `tile` >= 4 adjacent iz over all ny: the 2D
+//           column pass on the (ny x nz) plane.  The tile is never wider than nz (a plane with
+//           nz < 1024/ny is taken whole: one workgroup per ix);
+//   x pass  (COL layout) the field as an nx x (ny nz) matrix: a workgroup owns `tile` >= 4 adjacent
+//           flattened (iy, iz) columns over all nx rows.
+// The tile sits in LDS as it lies in memory ([line][iz] / [i][column]); the radix-2 Stockham
+// passes run on all of the tile's transforms at once with lanes walking the contiguous index
+// fastest, so every LDS and global access of a wave is a run of contiguous 16-B elements and
+// each row of a column tile is a contiguous segment of >= 64 B.
+//
+// gpe2d.hip is left as it is (its code object stays the parent's bit for bit); this file carries
+// its own copy of the pass template, generalised by a plane index and a row stride.
+//
+// All pointwise work is fused into the passes: record 0 and the very first N ride on the first
+// z pass's way into LDS; the 1/n scale, N, the record, the next step's first N and the final
+// field on the x pass's way out.  One L is three launches (z, y, x), so a Strang step is 3
+// launches and a Yoshida step 12; a call with no steps is one launch; there is no other kernel.
+// A pass updates the field in place: a workgroup reads its whole tile before it writes it, and
+// tiles are disjoint.  The only ordering between passes is the launch boundary on the stream:
+// no cooperative launch, no grid barrier, no flag another workgroup waits on, no float
+// accumulation across workgroups and no memory location that two workgroups of a launch both
+// touch.  A tile never spans two trajectories and the arithmetic of a point does not depend on
+// the thread that runs it, so results are bit-deterministic and independent of B.
+//
+// LDS: two ping-pong buffers of n * tile points plus n/2 twiddles and n phase factors, 16 B
+// each.  tile * n = 1024 points where the geometry allows (one butterfly per thread of a
+// 512-thread workgroup): 32.8 KiB at n = 32, 33.5 KiB at n = 64 (four workgroups per CU).  The
+// column tiles keep at least 4 columns, so they hold 2048 points (76 KiB) at n = 512 and 4096
+// points (152 KiB of the CU's 160 KiB) at n = 1024, which is what bounds BLINDNO_GPE3D_MAX_N.
+// Every offset is 64-bit.  fp64 throughout; contraction is off so a complex product rounds like
+// numpy's.
+#include "common.h"
+#include "blindno.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+struct __attribute__((aligned(16))) cd {
+  double re, im;
+};
+
+__device__ __forceinline__ cd cmul(cd a, cd b) {
+  return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re};
+}
+
+constexpr int kMinN = BLINDNO_GPE3D_MIN_N, kMaxN = BLINDNO_GPE3D_MAX_N;
+constexpr int64_t kMaxCells = BLINDNO_GPE3D_MAX_CELLS;
+constexpr int kTilePoints = 1024;        // points of a workgroup's tile (per ping-pong buffer)
+constexpr int kMinCols = 4;              // column tile: 4 x 16 B = 64-B row segments at least
+constexpr int kMaxThreads = 512;
+constexpr int kTrapzBlock = 512;
+
+struct PassArgs {
+  const double* src;      // field read: psi0 on the first launch, the scratch field afterwards
+  int64_t src_bstride;    // doubles per trajectory of src (0: one psi0 shared by the batch)
+  double* field;          // (B, nx, ny, nz, 2) scratch field written
+  const double* V;        // (B, nx, ny, nz)
+  const double* g;        // (B)
+  const double* kappa;    // (B)
+  double* rec_abs64;      // (B, nrec, nx, ny, nz) or NULL
+  float* rec_abs32;       // the same in fp32 or NULL
+  double* rec_psi;        // (B, nrec, nx, ny, nz, 2) or NULL
+  double* psi_out;        // (B, nx, ny, nz, 2), written when write_out
+  int64_t cells;          // nx ny nz
+  int64_t plane_stride;   // COL: points between two planes (y pass: ny nz; x pass: unused)
+  int64_t row_stride;     // COL: points between two rows of a tile (y pass: nz; x pass: ny nz)
+  int tiles_pp;           // tiles per plane
+  int tiles;              // tiles per trajectory = planes * tiles_pp
+  int nrec;
+  int tile, lg_tile;      // lines / columns per workgroup
+  int lg_n;               // log2 of the transform length
+  int do_lin;             // 0: no transform (nsteps = 0: record and copy only)
+  double lin_h;           // L(lin_h) along this axis
+  double d;               // grid spacing along this axis
+  int rec_pre;            // record index written before anything else, or -1
+  int has_pre;            // N(h_pre) before the transform
+  double h_pre;
+  int has_post1;          // after the transform: N(h_post1), record rec_post, N(h_post2)
+  double h_post1;
+  int rec_post;
+  int has_post2;
+  double h_post2;
+  int write_out;
+};
+
+// psi <- exp(-i h (V + g|psi|^2 + kappa|psi|^4)) psi
+__device__ __forceinline__ cd nonlinear(cd p, double V, double g, double kappa, double h) {
+  const double a2 = p.re * p.re + p.im * p.im;
+  const double A = V + g * a2 + kappa * (a2 * a2);
+  double s, c;
+  sincos(-h * A, &s, &c);
+  return cmul({c, s}, p);
+}
+
+// One radix-2 Stockham pass over the tile's `cnt` transforms of length n at once.  Point i of
+// transform q sits at q*n + i (ROW layout) or i*cnt + q (COL layout); butterfly t takes the
+// contiguous index from its low bits.  With `lin` the inputs are multiplied by the phase table
+// first (the kinetic factor, folded into the first inverse pass).
+template <bool COL, bool INV>
+__device__ __forceinline__ void fft_pass(const cd* __restrict__ src, cd* __restrict__ dst,
+                                         const cd* __restrict__ tw, const cd* __restrict__ lin,
+                                         int lg_n, int lg_cnt, int Ns) {
+  const int n = 1 << lg_n, half = n >> 1, cnt = 1 << lg_cnt;
+  const int tstride = half / Ns;
+  const int total = half << lg_cnt;
+  for (int t = threadIdx.x; t < total; t += blockDim.x) {
+    int j, q;
+    if (COL) {
+      q = t & (cnt - 1);
+      j = t >> lg_cnt;
+    } else {
+      j = t & (half - 1);
+      q = t >> (lg_n - 1);
+    }
+    const int base = COL ? q : q << lg_n;
+    const int es = COL ? cnt : 1;
+    const int k = j & (Ns - 1);
+    cd w = tw[k * tstride];
+    if (INV) w.im = -w.im;
+    cd a0 = src[base + j * es];
+    cd a1 = src[base + (j + half) * es];
+    if (lin) {
+      a0 = cmul(a0, lin[j]);
+      a1 = cmul(a1, lin[j + half]);
+    }
+    a1 = cmul(a1, w);
+    const int d = ((j - k) << 1) + k;
+    dst[base + d * es] = {a0.re + a1.re, a0.im + a1.im};
+    dst[base + (d + Ns) * es] = {a0.re - a1.re, a0.im - a1.im};
+  }
+}
+
+template <bool COL>
+__global__ __launch_bounds__(kMaxThreads) void gpe3d_pass_kernel(const PassArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int n = 1 << a.lg_n, cnt = a.tile;
+  const int points = n << a.lg_tile;
+  cd* buf0 = reinterpret_cast<cd*>(smem_raw);
+  cd* buf1 = buf0 + points;
+  cd* tw = buf1 + points;     // n/2
+  cd* lin = tw + (n >> 1);    // n
+  const int b = (int)blockIdx.x / a.tiles;
+  const int r = (int)blockIdx.x - b * a.tiles;          // tile of the trajectory
+  const int plane = r / a.tiles_pp;
+  const int t0 = (r - plane * a.tiles_pp) << a.lg_tile; // first line / column of the tile
+  const int64_t N = a.cells;
+  const double g = a.g[b], kappa = a.kappa[b];
+  const double* Vb = a.V + (int64_t)b * N;
+  // first point of the tile inside the trajectory (ROW: plane = 0 and t0 counts lines)
+  const int64_t origin = COL ? (int64_t)plane * a.plane_stride + t0 : (int64_t)t0 << a.lg_n;
+  // global point of LDS point e, inside the trajectory
+  auto gidx = [&](int e) -> int64_t {
+    return COL ? origin + (int64_t)(e >> a.lg_tile) * a.row_stride + (e & (cnt - 1)) : origin + e;
+  };
+  auto record = [&](cd p, int rec, int64_t gi) {
+    const int64_t o = ((int64_t)b * a.nrec + rec) * N + gi;
+    if (a.rec_abs64) a.rec_abs64[o] = hypot(p.re, p.im);
+    if (a.rec_abs32) a.rec_abs32[o] = (float)hypot(p.re, p.im);
+    if (a.rec_psi) *reinterpret_cast<cd*>(a.rec_psi + 2 * o) = p;
+  };
+
+  if (a.do_lin) {
+    for (int i = threadIdx.x; i < (n >> 1); i += blockDim.x) {
+      double s, c;
+      sincospi(2.0 * (double)i / (double)n, &s, &c);
+      tw[i] = {c, -s};
+    }
+    // k = 2 pi fftfreq(n, d): j / (n d) for j < (n+1)/2, else (j - n) / (n d)
+    const double val = 1.0 / ((double)n * a.d);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+      const int f = i < (n + 1) / 2 ? i : i - n;
+      const double k = 6.283185307179586 * ((double)f * val);
+      double s, c;
+      sincos((-a.lin_h * 0.5) * (k * k), &s, &c);
+      lin[i] = {c, s};
+    }
+  }
+  const double* src = a.src + (int64_t)b * a.src_bstride;
+  for (int e = threadIdx.x; e < points; e += blockDim.x) {
+    const int64_t gi = gidx(e);
+    cd p = *reinterpret_cast<const cd*>(src + 2 * gi);
+    if (a.rec_pre >= 0) record(p, a.rec_pre, gi);
+    if (a.has_pre) p = nonlinear(p, Vb[gi], g, kappa, a.h_pre);
+    buf0[e] = p;
+  }
+  __syncthreads();
+
+  cd* bufs[2] = {buf0, buf1};
+  int cur = 0;
+  double scale = 1.0;
+  if (a.do_lin) {
+    for (int Ns = 1; Ns < n; Ns <<= 1) {
+      fft_pass<COL, false>(bufs[cur], bufs[cur ^ 1], tw, nullptr, a.lg_n, a.lg_tile, Ns);
+      cur ^= 1;
+      __syncthreads();
+    }
+    for (int Ns = 1; Ns < n; Ns <<= 1) {
+      fft_pass<COL, true>(bufs[cur], bufs[cur ^ 1], tw, Ns == 1 ? lin : nullptr, a.lg_n,
+                          a.lg_tile, Ns);
+      cur ^= 1;
+      __syncthreads();
+    }
+    scale = 1.0 / (double)n;   // numpy.fft.ifft's normalisation; a power of two, so exact
+  }
+  const cd* res = bufs[cur];
+  double* fb = a.field + 2 * (int64_t)b * N;
+  double* ob = a.write_out ? a.psi_out + 2 * (int64_t)b * N : nullptr;
+  for (int e = threadIdx.x; e < points; e += blockDim.x) {
+    const int64_t gi = gidx(e);
+    cd p = res[e];
+    p.re = p.re * scale;
+    p.im = p.im * scale;
+    if (a.has_post1 || a.has_post2) {
+      const double v = Vb[gi];
+      if (a.has_post1) p = nonlinear(p, v, g, kappa, a.h_post1);
+      if (a.rec_post >= 0) record(p, a.rec_post, gi);
+      if (a.has_post2) p = nonlinear(p, v, g, kappa, a.h_post2);
+    } else if (a.rec_post >= 0) {
+      record(p, a.rec_post, gi);
+    }
+    *reinterpret_cast<cd*>(fb + 2 * gi) = p;
+    if (a.write_out) *reinterpret_cast<cd*>(ob + 2 * gi) = p;
+  }
+}
+
+// trapezoid weight of point i of a grid: half the sum of the two adjacent spacings (one at an end)
+__device__ __forceinline__ double trapz_w(const double* __restrict__ x, int i, int n) {
+  return 0.5 * ((i > 0 ? x[i] - x[i - 1] : 0.0) + (i < n - 1 ? x[i + 1] - x[i] : 0.0));
+}
+
+// out[2f] = trapz_z(trapz_y(trapz_x((a_f - b_f)^2))), out[2f+1] the same of b_f^2, as the weighted
+// sum over the frame's points with the weights wx(ix) wy(iy) wz(iz).  The entry has no scratch
+// argument and allocates nothing, so a frame is one workgroup and the reduction has two stages
+// inside it, both in a fixed order: each thread sums its points e = tid, tid + 512, ... in
+// ascending order, then a binary tree over the 512 partial sums in LDS.
+__global__ __launch_bounds__(kTrapzBlock) void trapz3_frames_kernel(
+    const double* __restrict__ a, const double* __restrict__ b, const double* __restrict__ x,
+    const double* __restrict__ y, const double* __restrict__ z, double* __restrict__ out, int nx,
+    int ny, int nz) {
+  __shared__ double ra[kTrapzBlock], rb[kTrapzBlock];
+  const int64_t plane = (int64_t)ny * nz;
+  const int64_t N = (int64_t)nx * plane;
+  const double* ap = a + (int64_t)blockIdx.x * N;
+  const double* bp = b + (int64_t)blockIdx.x * N;
+  double sa = 0.0, sb = 0.0;
+  for (int64_t e = threadIdx.x; e < N; e += kTrapzBlock) {
+    const int ix = (int)(e / plane);
+    const int64_t r = e - (int64_t)ix * plane;
+    const int iy = (int)(r / nz), iz = (int)(r - (int64_t)iy * nz);
+    const double w = (trapz_w(x, ix, nx) * trapz_w(y, iy, ny)) * trapz_w(z, iz, nz);
+    const double bv = bp[e], d = ap[e] - bv;
+    sa += w * (d * d);
+    sb += w * (bv * bv);
+  }
+  ra[threadIdx.x] = sa;
+  rb[threadIdx.x] = sb;
+  __syncthreads();
+  for (int s = kTrapzBlock / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) {
+      ra[threadIdx.x] += ra[threadIdx.x + s];
+      rb[threadIdx.x] += rb[threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out[2 * (int64_t)blockIdx.x] = ra[0];
+    out[2 * (int64_t)blockIdx.x + 1] = rb[0];
+  }
+}
+
+int ilog2(int64_t v) {
+  int l = 0;
+  while (((int64_t)1 << l) < v) ++l;
+  return l;
+}
+
+bool pow2_in_range(int v) { return v >= kMinN && v <= kMaxN && (v & (v - 1)) == 0; }
+
+int64_t min_i64(int64_t a, int64_t b) { return a < b ? a : b; }
+int64_t max_i64(int64_t a, int64_t b) { return a > b ? a : b; }
+
+// z-lines per workgroup of the z pass; columns per workgroup of the y pass (adjacent iz of one
+// plane) and of the x pass (adjacent flattened (iy, iz)).  All powers of two.
+int z_tile(int nx, int ny, int nz) { return (int)max_i64(1, min_i64((int64_t)nx * ny, kTilePoints / nz)); }
+int y_tile(int ny, int nz) { return (int)max_i64(kMinCols, min_i64(nz, kTilePoints / ny)); }
+int x_tile(int nx, int ny, int nz) { return (int)max_i64(kMinCols, min_i64((int64_t)ny * nz, kTilePoints / nx)); }
+
+struct Geometry {
+  int64_t cells;
+  int zt, yt, xt;               // tile widths
+  int64_t zb, yb, xb;           // workgroups per trajectory
+};
+
+bool gpe3d_grid(int B, int nx, int ny, int nz, Geometry* G) {
+  if (B <= 0 || !pow2_in_range(nx) || !pow2_in_range(ny) || !pow2_in_range(nz)) return false;
+  G->cells = (int64_t)nx * ny * nz;
+  if (G->cells > kMaxCells) return false;
+  G->zt = z_tile(nx, ny, nz);
+  G->yt = y_tile(ny, nz);
+  G->xt = x_tile(nx, ny, nz);
+  G->zb = (int64_t)nx * ny / G->zt;
+  G->yb = (int64_t)nx * (nz / G->yt);
+  G->xb = (int64_t)ny * nz / G->xt;
+  // a launch's workgroup count must fit the grid's x dimension
+  return (int64_t)B * max_i64(G->zb, max_i64(G->yb, G->xb)) <= 0x7fffffff;
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+template <bool COL>
+hipError_t launch_pass(const PassArgs& a, int B, hipStream_t st) {
+  const int n = 1 << a.lg_n;
+  const int points = n << a.lg_tile;
+  const size_t sh = sizeof(cd) * (2 * (size_t)points + n / 2 + n);
+  if (sh > 64 * 1024) {
+    // more dynamic LDS than the default cap; a refusal surfaces as the launch's own error
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gpe3d_pass_kernel<COL>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+    (void)hipGetLastError();
+  }
+  const int threads = (int)max_i64(64, min_i64(kMaxThreads, points / 2));
+  gpe3d_pass_kernel<COL><<<(unsigned)((int64_t)B * a.tiles), threads, sh, st>>>(a);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+BLINDNO_API int64_t blindno_gpe3d_scratch_doubles(int B, int nx, int ny, int nz) {
+  Geometry G;
+  if (!gpe3d_grid(B, nx, ny, nz, &G)) return -1;
+  return 2 * (int64_t)B * G.cells;
+}
+
+BLINDNO_API int64_t blindno_gpe3d_launches(int nsteps, int order) {
+  if (nsteps < 0 || (order != 2 && order != 4)) return -1;
+  return nsteps == 0 ? 1 : (int64_t)nsteps * (order == 2 ? 3 : 12);
+}
+
+BLINDNO_API int blindno_gpe3d_solve(const double* psi0, const double* V, const double* g,
+                                    const double* kappa, double dx, double dy, double dz, double dt,
+                                    int nsteps, int order, int rec_every, void* rec_abs,
+                                    int rec_abs_f32, double* rec_psi, double* psi_out, double* scratch,
+                                    int B, int nx, int ny, int nz, int psi0_batched, void* stream) {
+  Geometry G;
+  if (!gpe3d_grid(B, nx, ny, nz, &G) || nsteps < 0 || rec_every < 1 ||
+      (order != 2 && order != 4) || !psi0 || !V || !g || !kappa || !scratch ||
+      (rec_abs_f32 != 0 && rec_abs_f32 != 1) || !(dx > 0.0) || !(dy > 0.0) || !(dz > 0.0) ||
+      !aligned16(psi0) || !aligned16(scratch) || !aligned16(rec_psi) || !aligned16(psi_out))
+    return (int)hipErrorInvalidValue;
+  const int64_t N = G.cells;
+  const int nrec = nsteps / rec_every + 1;
+  // the largest byte offset formed is 16 B nrec N (the psi record): it must fit 63 bits
+  if ((rec_abs || rec_psi) && (double)B * (double)nrec * (double)N * 16.0 >= 9.0e18)
+    return (int)hipErrorInvalidValue;
+  hipStream_t st = (hipStream_t)stream;
+  PassArgs base = {};
+  base.field = scratch;
+  base.V = V;
+  base.g = g;
+  base.kappa = kappa;
+  base.rec_abs64 = rec_abs_f32 ? nullptr : (double*)rec_abs;
+  base.rec_abs32 = rec_abs_f32 ? (float*)rec_abs : nullptr;
+  base.rec_psi = rec_psi;
+  base.psi_out = psi_out;
+  base.cells = N;
+  base.nrec = nrec;
+  base.rec_pre = base.rec_post = -1;
+  base.src = scratch;
+  base.src_bstride = 2 * N;
+
+  PassArgs pz = base, py = base, px = base;
+  pz.tile = G.zt;                        // z: whole lines, one "plane"
+  pz.lg_tile = ilog2(G.zt);
+  pz.lg_n = ilog2(nz);
+  pz.d = dz;
+  pz.tiles_pp = pz.tiles = (int)G.zb;
+  py.tile = G.yt;                        // y: per ix, adjacent iz over all ny
+  py.lg_tile = ilog2(G.yt);
+  py.lg_n = ilog2(ny);
+  py.d = dy;
+  py.plane_stride = (int64_t)ny * nz;
+  py.row_stride = nz;
+  py.tiles_pp = nz / G.yt;
+  py.tiles = (int)G.yb;
+  px.tile = G.xt;                        // x: adjacent (iy, iz) over all nx
+  px.lg_tile = ilog2(G.xt);
+  px.lg_n = ilog2(nx);
+  px.d = dx;
+  px.row_stride = (int64_t)ny * nz;
+  px.tiles_pp = px.tiles = (int)G.xb;
+  pz.src = psi0;                         // the first launch reads psi0 and records step 0
+  pz.src_bstride = psi0_batched ? 2 * N : 0;
+  pz.rec_pre = 0;
+
+  if (nsteps == 0) {
+    pz.do_lin = 0;
+    pz.write_out = psi_out != nullptr;
+    return (int)launch_pass<false>(pz, B, st);
+  }
+  // Yoshida coefficients as the reference forms them (2**(1/3) = pow(2, 1/3))
+  const double cr = pow(2.0, 1.0 / 3.0);
+  const double c2 = 2.0 - cr;
+  const double a1 = 1.0 / c2, a2 = -cr / c2;
+  // per step: N(hn[0]) L(hl[0]) N(hn[1]) ... L(hl[nl-1]) N(hn[nl])
+  const int nl = order == 2 ? 1 : 4;
+  const double hn2[2] = {dt / 2, dt / 2}, hl2[1] = {dt};
+  const double hn4[5] = {a1 * dt, a2 * dt, a1 * dt, a2 * dt, a1 * dt};
+  const double hl4[4] = {a1 * dt, a2 * dt, a2 * dt, a1 * dt};
+  const double* hn = order == 2 ? hn2 : hn4;
+  const double* hl = order == 2 ? hl2 : hl4;
+  pz.do_lin = py.do_lin = px.do_lin = 1;
+  pz.has_pre = 1;                        // the first step's first N; later ones ride on the
+  pz.h_pre = hn[0];                      // previous step's x pass (has_post2)
+  for (int n = 1; n <= nsteps; ++n) {
+    for (int l = 0; l < nl; ++l) {
+      pz.lin_h = py.lin_h = px.lin_h = hl[l];
+      hipError_t e = launch_pass<false>(pz, B, st);
+      if (e != hipSuccess) return (int)e;
+      pz.src = scratch;
+      pz.src_bstride = 2 * N;
+      pz.rec_pre = -1;
+      pz.has_pre = 0;
+      e = launch_pass<true>(py, B, st);
+      if (e != hipSuccess) return (int)e;
+      const bool last = l == nl - 1;
+      px.has_post1 = 1;
+      px.h_post1 = hn[l + 1];
+      px.rec_post = last && n % rec_every == 0 ? n / rec_every : -1;
+      px.has_post2 = last && n < nsteps;
+      px.h_post2 = hn[0];
+      px.write_out = last && n == nsteps && psi_out != nullptr;
+      e = launch_pass<true>(px, B, st);
+      if (e != hipSuccess) return (int)e;
+    }
+  }
+  return (int)hipSuccess;
+}
+
+BLINDNO_API int blindno_trapz3_frames(const double* a, const double* b, const double* x,
+                                      const double* y, const double* z, double* out, int frames,
+                                      int nx, int ny, int nz, void* stream) {
+  if (frames <= 0 || nx < 1 || ny < 1 || nz < 1 || !a || !b || !x || !y || !z || !out)
+    return (int)hipErrorInvalidValue;
+  trapz3_frames_kernel<<<frames, kTrapzBlock, 0, (hipStream_t)stream>>>(a, b, x, y, z, out, nx, ny, nz);
+  return (int)hipGetLastError();
+}

@@ -1,0 +1,188 @@
+"""3D GPE: the binding of include/blindno_gpe3d.h, the numpy checker tests/gpe3d_ref.py that the
+GPU tests compare against, the generator's draws and the request guards of solve_batch_3d (no GPU
+needed).
+
+PARITY UNPINNED in three dimensions (the reference has no 3D GPE code): the checker is gpe3d_ref,
+tied to the reference's own numbers through its reduction to gpe2d_ref -- itself reduced to the 1D
+oracle and the goldens by tests/test_gpe2d.py -- when nothing depends on one axis.
+"""
+import glob
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import gpe2d_ref
+import gpe3d_ref
+from conftest import ROOT, rel_l2
+from oracle import gpe_ref
+
+
+def test_gpe3d_symbols_declared_and_bound():
+    """include/blindno_gpe3d.h (included by blindno.h) <=> _lib.SIGNATURES_GPE3D <=> the library."""
+    import blindno
+    from blindno import _lib
+    assert '#include "blindno_gpe3d.h"' in open(os.path.join(ROOT, "include", "blindno.h")).read()
+    hdr = open(os.path.join(ROOT, "include", "blindno_gpe3d.h")).read()
+    decl = sorted(set(re.findall(r"^(?:int|int64_t|const char\*)\s+(blindno_\w+)\(", hdr, re.M)))
+    assert decl == sorted(_lib.SIGNATURES_GPE3D) and len(decl) == 4
+    assert {"blindno_gpe3d_solve", "blindno_trapz3_frames"} <= set(decl)
+    others = (set(_lib.SIGNATURES) | set(_lib.SIGNATURES_CONV3D) | set(_lib.SIGNATURES_FPE) |
+              set(_lib.SIGNATURES_GPE2D) | set(_lib.SIGNATURES_BAG3D))
+    assert not set(_lib.SIGNATURES_GPE3D) & others
+    lib = blindno.load_library()
+    for s in decl:
+        assert hasattr(lib, s) and s in _lib.exported_symbols(), s
+        m = re.search(r"\b(?:int|int64_t)\s+" + s + r"\s*\(([^;]*)\)\s*;", hdr)
+        nargs = len([a for a in m.group(1).split(",") if a.strip()])
+        assert nargs == len(_lib.SIGNATURES_GPE3D[s]) == len(getattr(lib, s).argtypes), (s, nargs)
+    # the 2D entries argument for argument, with dz and nz added
+    assert len(_lib.SIGNATURES_GPE3D["blindno_gpe3d_solve"]) == len(_lib.SIGNATURES_GPE2D["blindno_gpe2d_solve"]) + 2
+    assert len(_lib.SIGNATURES_GPE3D["blindno_trapz3_frames"]) == len(_lib.SIGNATURES_GPE2D["blindno_trapz2_frames"]) + 2
+    # the limits are macros of the header
+    lim = {k: v for k, v in re.findall(r"#define (BLINDNO_GPE3D_\w+) (.+)", hdr)}
+    assert lim["BLINDNO_GPE3D_MIN_N"] == "4" and int(lim["BLINDNO_GPE3D_MAX_N"]) == 1024
+    max_cells = eval(lim["BLINDNO_GPE3D_MAX_CELLS"])
+    assert max_cells == 1 << 24
+    # the host-only queries: one working field, int64; -1 for a refused grid
+    q = lambda *a: _lib.query("blindno_gpe3d_scratch_doubles", *a)   # noqa: E731
+    assert q(16, 64, 64, 64) == 2 * 16 * 64 ** 3
+    assert q(1024, 256, 256, 256) == 2 * 1024 * 256 ** 3 > 2 ** 34
+    assert q(1, 1024, 4, 4) > 0 and q(1, 4, 1024, 4) > 0 and q(1, 4, 4, 1024) > 0
+    assert q(1, 1024, 128, 128) == 2 * max_cells and q(1, 1024, 128, 256) == -1 and q(1, 512, 256, 256) == -1
+    for bad in [(0, 8, 8, 8), (1, 2, 8, 8), (1, 8, 2, 8), (1, 8, 8, 2), (1, 12, 8, 8), (1, 8, 12, 8), (1, 8, 8, 12),
+                (1, 8, 8, 2048), (1, 2048, 4, 4), (1, 0, 8, 8), (1, 8, 8, -4)]:
+        assert q(*bad) == -1, bad
+    n = lambda *a: _lib.query("blindno_gpe3d_launches", *a)          # noqa: E731
+    assert (n(1000, 2), n(1000, 4), n(0, 2), n(0, 4), n(5, 3), n(-1, 2)) == (3000, 12000, 1, 1, -1, -1)
+    csrc = os.path.join(ROOT, "reconstruction-of-pde-without-time-label_amd", "csrc")
+    src = open(os.path.join(csrc, "gpe3d.hip")).read()
+    assert "atomic" not in src.lower() and "hipLaunchCooperativeKernel" not in src
+    assert "gpe3d.hip" in [os.path.basename(p) for p in glob.glob(os.path.join(csrc, "*.hip"))]
+
+
+def _problem2(n1, n2, seed=0):
+    rs = np.random.RandomState(seed)
+    a = np.linspace(-10, 10, n1)
+    b = np.linspace(-8, 8, n2)
+    V = gpe2d_ref.training_potentials(1, a, b, rs)[0]
+    psi0 = (gpe_ref.initial_condition(2, a)[:, None] * gpe_ref.initial_condition(3, b)[None, :]).astype(complex)
+    return a, b, V, psi0 * np.exp(0.3j * a)[:, None]
+
+
+@pytest.mark.parametrize("order", [2, 4])
+@pytest.mark.parametrize("axis", [0, 1, 2])
+def test_checker_reduces_to_the_2d_checker(axis, order):
+    """psi0 and V constant along one axis: the 3D transform has only that axis' k = 0 bin, whose
+    phase is 1, so every slice across it is the 2D integrator's trajectory on the other two axes
+    (in their order)."""
+    a, b, V2, p2 = _problem2(8, 16, seed=axis)
+    c = np.linspace(-3, 3, 4)
+    _, r2, f2 = gpe2d_ref.solve(p2, a, b, 0.005, 0.1, order, 1.5, 0.7, V2, rec_every=3)
+    grids = [a, b]
+    grids.insert(axis, c)
+    rep = lambda f: np.repeat(np.expand_dims(f, axis), 4, axis)       # noqa: E731
+    t, r3, f3 = gpe3d_ref.solve(rep(p2), *grids, 0.005, 0.1, order, 1.5, 0.7, rep(V2), rec_every=3)
+    assert r3.shape == (7, *[len(g) for g in grids]) and np.allclose(t, np.linspace(0, 0.1, 21)[::3])
+    for s in range(4):
+        e = rel_l2(np.take(r3, s, axis + 1), r2)
+        assert e <= 1e-12, (axis, s, e)
+        assert rel_l2(np.take(f3, s, axis), f2) <= 1e-12
+
+
+def test_checker_record_schedule_and_mass():
+    x, y, z = np.linspace(-10, 10, 8), np.linspace(-8, 8, 4), np.linspace(-6, 6, 16)
+    V = gpe3d_ref.training_potentials(1, x, y, z, np.random.RandomState(1))[0]
+    psi0 = gpe3d_ref.initial_field(x, y, z) * np.exp(0.2j * z)[None, None, :]
+    t, r, f = gpe3d_ref.solve(psi0, x, y, z, 0.01, 0.2, 4, 1.0, 1.0, V, rec_every=7)    # 20 steps: 0, 7, 14
+    full = gpe3d_ref.solve(psi0, x, y, z, 0.01, 0.2, 4, 1.0, 1.0, V)[1]
+    assert r.shape[0] == 3 and np.array_equal(r, full[::7]) and np.array_equal(f, full[-1])
+    assert np.allclose(t, [0, 0.07, 0.14])
+    m = (np.abs(full) ** 2).sum((1, 2, 3))
+    assert np.abs(m / m[0] - 1).max() <= 1e-12
+
+
+def test_generator_draw_order_and_keys():
+    """The draws are a, b, c, x0, y0, z0 per orbit, from the given rng, and nothing else; the
+    generator's dict feeds ParameterDataset with one more axis, 1D and 2D items unchanged."""
+    from blindno import data, gpe
+    x, y, z = np.linspace(-10, 10, 8), np.linspace(-10, 10, 4), np.linspace(-10, 10, 16)
+    rs0 = np.random.RandomState(5)
+    V = gpe.training_potentials_3d(3, x, y, z, rs0)
+    rs = np.random.RandomState(5)
+    X, Y, Z = x[:, None, None], y[None, :, None], z[None, None, :]
+    for m in range(3):
+        a, b, c = rs.uniform(0.1, 0.3), rs.uniform(0.5, 2), rs.uniform(0.5, 2)
+        x0, y0, z0 = rs.uniform(-3, 3), rs.uniform(-3, 3), rs.uniform(-3, 3)
+        want = a * ((X - x0) ** 2 + (Y - y0) ** 2 + (Z - z0) ** 2) + \
+            b * np.cos(c * (X - x0)) ** 2 * np.cos(c * (Y - y0)) ** 2 * np.cos(c * (Z - z0)) ** 2
+        assert V[m].shape == (8, 4, 16) and np.allclose(V[m], want, rtol=1e-14, atol=0)
+    assert rs0.uniform() == rs.uniform()                       # 18 draws consumed, no more
+    assert np.allclose(V, gpe3d_ref.training_potentials(3, x, y, z, np.random.RandomState(5)), rtol=1e-14, atol=0)
+    d = gpe3d_ref.generate(3, 8, 4, 16, dt=0.01, t_final=0.2, rng=np.random.RandomState(5))
+    assert sorted(d) == ["V", "g", "kappa", "y"]
+    assert d["y"].shape == (3, 3, 8, 4, 16) and d["V"].shape == (3, 8, 4, 16) and d["g"].shape == d["kappa"].shape == (3,)
+    ds = data.ParameterDataset(arrays=d)
+    xi, yi = ds[1]
+    assert len(ds) == 3 and xi.shape == (3, 8, 4, 16) and yi.shape == (8, 4, 16, 1)
+    assert xi.dtype == yi.dtype == torch.float32 and ds.targets().shape == (3, 8, 4, 16, 1)
+    Xd, Yd = data.device_tensors(ds, [0, 2], device="cpu")
+    assert Xd.shape == (2, 3, 8, 4, 16) and Yd.shape == (2, 8, 4, 16, 1)
+
+
+def test_requests_over_the_limits_are_refused_before_launch():
+    """MAX_LAUNCHES_3D and MAX_RECORD_BYTES are checked before anything touches the device
+    (device='cpu' raises the no-CPU-path error next), and each message names its limit."""
+    from blindno import gpe
+    from blindno._lib import BlindnoError
+    assert gpe.MAX_LAUNCHES_3D & (gpe.MAX_LAUNCHES_3D - 1) == 0
+    x = np.linspace(-10, 10, 8)
+    V = np.zeros((8, 8, 8))
+    p = np.ones((8, 8, 8), complex)
+    steps = gpe.MAX_LAUNCHES_3D // 3                              # 3 launches per Strang step
+    with pytest.raises(BlindnoError, match="no CPU path"):
+        gpe.solve_batch_3d(p, x, x, x, 1.0, steps + 0.5, 2, 1, 1, V, rec_every=steps, device="cpu")
+    with pytest.raises(BlindnoError, match=r"MAX_LAUNCHES_3D.*refusing to launch"):
+        gpe.solve_batch_3d(p, x, x, x, 1.0, steps + 1.5, 2, 1, 1, V, rec_every=steps, device="cpu")
+    with pytest.raises(BlindnoError, match=r"MAX_LAUNCHES_3D.*refusing to launch"):
+        gpe.solve_batch_3d(p, x, x, x, 1.0, gpe.MAX_LAUNCHES_3D // 12 + 1.5, 4, 1, 1, V, rec_every=steps, device="cpu")
+    # B = 64 with 1001 frames at 64^3 is 134 GB of fp64 |psi|
+    x = np.linspace(-10, 10, 64)
+    V = np.broadcast_to(np.zeros((1, 64, 64, 64)), (64, 64, 64, 64))
+    p = np.ones((64, 64, 64), complex)
+    with pytest.raises(BlindnoError, match=r"MAX_RECORD_BYTES.*refusing to launch"):
+        gpe.solve_batch_3d(p, x, x, x, 0.005, 5.0, 2, 2, 2, V, device="cpu")
+    with pytest.raises(BlindnoError, match="no CPU path"):            # every 10th frame, fp32: 6.8 GB
+        gpe.solve_batch_3d(p, x, x, x, 0.005, 5.0, 2, 2, 2, V, rec_every=10, abs_dtype=torch.float32, device="cpu")
+    with pytest.raises(BlindnoError, match="no CPU path"):            # the generator's default batch, fp64
+        gpe.solve_batch_3d(p, x, x, x, 0.005, 5.0, 2, 2, 2, V[:16], rec_every=10, device="cpu")
+    with pytest.raises(BlindnoError, match="MAX_RECORD_BYTES"):        # psi counts too
+        gpe.solve_batch_3d(p, x, x, x, 0.005, 5.0, 2, 2, 2, V, rec_every=10, want_abs=False, want_psi=True,
+                           device="cpu")
+    x8 = x[:8]
+    for kw, pat in [(dict(order=3), "order"), (dict(rec_every=0), "rec_every"), (dict(abs_dtype=torch.float16), "abs_dtype")]:
+        args = dict(order=2, rec_every=1)
+        args.update(kw)
+        order = args.pop("order")
+        with pytest.raises(BlindnoError, match=pat):
+            gpe.solve_batch_3d(np.ones((8, 8, 8), complex), x8, x8, x8, 0.1, 1.0, order, 1, 1, np.zeros((8, 8, 8)),
+                               device="cpu", **args)
+    for n in (6, 2, 2048):
+        xs = np.linspace(-1, 1, n)
+        for ax in range(3):
+            shape = [8, 8, 8]
+            shape[ax] = n
+            grids = [x8, x8, x8]
+            grids[ax] = xs
+            with pytest.raises(BlindnoError, match="power of two"):
+                gpe.solve_batch_3d(np.broadcast_to(1 + 0j, shape), *grids, 0.1, 1.0, 2, 1, 1,
+                                   np.broadcast_to(0.0, shape), device="cpu")
+    with pytest.raises(BlindnoError, match="2\\^24"):
+        xs = np.linspace(-1, 1, 512)
+        sh = (512, 256, 256)
+        gpe.solve_batch_3d(np.broadcast_to(1 + 0j, sh), xs, xs[:256], xs[:256], 0.1, 1.0, 2, 1, 1,
+                           np.broadcast_to(0.0, sh), device="cpu")
+    with pytest.raises(BlindnoError, match="V has shape"):
+        gpe.solve_batch_3d(np.ones((8, 8, 8), complex), x8, x8, x8, 0.1, 1.0, 2, 1, 1, np.zeros((8, 8)), device="cpu")

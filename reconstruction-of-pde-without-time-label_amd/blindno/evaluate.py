@@ -31,7 +31,11 @@ KINDS = {
     # kind: (target npz keys / scales, output names, metric header)
     "2d_FPE": dict(fields=("drift", "diffusion"), header=["index", "rel_l2_drift", "rel_l2_diffusion"]),
     "2d_Non_conservative_FPE": dict(fields=("Fx", "Fy"), header=["index", "rel_l2_Fx", "rel_l2_Fy"]),
+    # the project's own 3D experiment (datagen.fpe_3d_dataset): data.TrajectoryDataset3D's scales and
+    # z-scoring, which are the 2D class's with one more axis
+    "3d_FPE": dict(fields=("drift", "diffusion"), header=["index", "rel_l2_drift", "rel_l2_diffusion"]),
 }
+FPE_KINDS = ("2d_FPE", "3d_FPE")          # potential + drag targets
 DRIFT_SCALE, DIFFUSION_SCALE, F_SCALE = 1e21, 1e6, 1e12
 
 
@@ -60,7 +64,7 @@ def compute_train_stats(kind: str, train) -> Dict[str, np.ndarray]:
     traj = np.array(data["trajectories"], dtype=np.float32) * TRAJ_SCALE
     st = {"traj_mean": traj.mean(axis=(0, 1), keepdims=True),
           "traj_std": traj.std(axis=(0, 1), keepdims=True) + 1e-8}
-    if kind == "2d_FPE":
+    if kind in FPE_KINDS:
         drift = np.array(data["potential"], dtype=np.float32) * DRIFT_SCALE
         diff = np.array(data["drag"], dtype=np.float32) * DIFFUSION_SCALE
         st.update(drift_mean=drift.mean(axis=0, keepdims=True), drift_std=drift.std(axis=0, keepdims=True) + 1e-8,
@@ -72,13 +76,14 @@ def compute_train_stats(kind: str, train) -> Dict[str, np.ndarray]:
 
 
 def normalize_input(traj_raw: np.ndarray, stats) -> np.ndarray:
-    """eval_fno.py:66-70 for one (T, Nx, Ny) trajectory."""
+    """eval_fno.py:66-70 for one (T, Nx, Ny) or (T, Nx, Ny, Nz) trajectory."""
     return (traj_raw * TRAJ_SCALE - stats["traj_mean"].squeeze(0)) / stats["traj_std"].squeeze(0)
 
 
 def denormalize(kind: str, pred: np.ndarray, stats):
-    """eval_fno.py:72-99 for one (Nx, Ny, 2) prediction -> two fields in original units."""
-    if kind == "2d_FPE":
+    """eval_fno.py:72-99 for one (Nx, Ny, 2) prediction -> two fields in original units
+    (3d_FPE: (Nx, Ny, Nz, 2))."""
+    if kind in FPE_KINDS:
         a = (pred[..., 0] * stats["drift_std"].squeeze(0) + stats["drift_mean"].squeeze(0)) / DRIFT_SCALE
         b = (pred[..., 1] * stats["diff_std"].squeeze(0) + stats["diff_mean"].squeeze(0)) / DIFFUSION_SCALE
         return a, b
@@ -91,7 +96,7 @@ def denormalize(kind: str, pred: np.ndarray, stats):
 def true_fields(kind: str, data, index: int, stats):
     """The reference's normalise -> de-normalise round trip of the true fields
     (eval_fno.py:218-223; 2d_Non_conservative_FPE/eval_fno.py:261-267)."""
-    if kind == "2d_FPE":
+    if kind in FPE_KINDS:
         out = []
         for key, scale, m, s in (("potential", DRIFT_SCALE, "drift_mean", "drift_std"),
                                  ("drag", DIFFUSION_SCALE, "diff_mean", "diff_std")):
@@ -113,7 +118,7 @@ def grid2d(nx: int, ny: int, device) -> torch.Tensor:
 @torch.no_grad()
 def predict(model: torch.nn.Module, x: torch.Tensor, grid: torch.Tensor, batch: int = 8) -> torch.Tensor:
     """Eval-mode predictions (n, Nx, Ny, 2) of normalised bags x (n, T, Nx, Ny) in HBM,
-    ``batch`` samples per forward."""
+    ``batch`` samples per forward; 3D models: (n, Nx, Ny, Nz, 2) of x (n, T, Nx, Ny, Nz)."""
     was = model.training
     model.eval()
     try:
@@ -123,6 +128,8 @@ def predict(model: torch.nn.Module, x: torch.Tensor, grid: torch.Tensor, batch: 
     out = torch.cat(outs, 0)
     if out.dim() == 4 and out.shape[1] == 2 and out.shape[-1] != 2:
         out = out.permute(0, 2, 3, 1)
+    elif out.dim() == 5 and out.shape[1] == 2 and out.shape[-1] != 2:
+        out = out.permute(0, 2, 3, 4, 1)
     return out.contiguous()
 
 
@@ -137,11 +144,15 @@ def evaluate(kind: str, model: torch.nn.Module, train, test, indices: Iterable[i
     traj = np.asarray(data["trajectories"])
     M = traj.shape[0]
     idx = [i for i in indices if 0 <= i < M]
-    nx, ny = traj.shape[2], traj.shape[3]
     x = np.stack([normalize_input(np.array(traj[i], dtype=np.float32), stats) for i in idx]) if idx else \
         np.zeros((0,) + traj.shape[1:], np.float32)
     xd = torch.tensor(x, dtype=torch.float32, device=device)
-    pred = predict(model, xd, grid2d(nx, ny, device), batch).cpu().numpy() if idx else None
+    if kind == "3d_FPE":
+        from .timeerror import grid3d
+        grid = grid3d(*traj.shape[2:5], device)
+    else:
+        grid = grid2d(traj.shape[2], traj.shape[3], device)
+    pred = predict(model, xd, grid, batch).cpu().numpy() if idx else None
     rows = []
     writer = f_csv = None
     if outdir is not None:
@@ -339,7 +350,11 @@ def main(argv=None):
         return
     if a.model in one_d_unet.values():
         ap.error(f"--model {a.model} is a 1D model")
-    if a.model == "PermInvUNet_attn":
+    if a.experiment == "3d_FPE":
+        if a.model_given:
+            ap.error("3d_FPE evaluates the trainer's NIOFP3D_FNO(2, 8, 4, 2, input_modes=4); it takes no --model")
+        model = nio.NIOFP3D_FNO(2, 8, 4, 2, a.device, input_modes=4)
+    elif a.model == "PermInvUNet_attn":
         # 2d_FPE/eval_unet.py:156 (depth 4), 2d_Non_conservative_FPE/eval_unet.py:192 (depth 5)
         model = (unet.PermInvUNet_attn(1, 2, 1, 4, (a.nx, a.ny)) if a.experiment == "2d_FPE" else
                  unet.PermInvUNet_attn_NC(1, 2, 1, 5, (a.nx, a.ny)))

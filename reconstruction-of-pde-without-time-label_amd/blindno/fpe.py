@@ -23,7 +23,10 @@ Nsteps x substeps x Taylor degree stencil passes -- is ``blindno_fp_propagate``,
 LDS-resident workgroup per trajectory, many trajectories per launch (``propagate_many``), for 1D
 and 2D grids of at most 8192 cells, and ``blindno_fp_propagate_nd`` for larger ones and for 3D
 grids: the density stays in global memory and every Horner pass is one launch
-(tests/test_fpe_nd.py, tests/test_gpu_fpe_nd.py against tests/fpe3d_ref.py).
+(tests/test_fpe_nd.py, tests/test_gpu_fpe_nd.py against tests/fpe3d_ref.py).  An evaluator that
+wants only the density error against a reference trajectory calls ``propagate_error_many``
+(``blindno_fp_error_nd``): the same integrator with no record, the per-frame error sums reduced
+on the device (tests/test_fpe_err.py, tests/test_gpu_fpe_err.py).
 """
 from __future__ import annotations
 
@@ -308,3 +311,88 @@ def propagate_many(sims: Sequence[fokker_planck], initials, tf, Nsteps=None, dt=
         return res
     res = out.cpu().numpy()
     return [(time, res[k].reshape((Nsteps,) + grid_shape)) for k in range(len(sims))]
+
+
+def error_launch_plan(steps: Sequence[int], group: int, Nsteps: int, degree: int = TAYLOR_DEGREE):
+    """The launches of ``propagate_error_many`` for per-trajectory substep counts ``steps`` laid out
+    in consecutive groups of ``group`` (a pure function: no device).  A group stays whole and runs
+    with the largest count of its members (more substeps than a member needs is only more
+    accurate); groups of equal count share a launch.  Returns [(substeps, [group index, ...])] in
+    ascending substep order.  Raises BlindnoError for a layout that is not whole groups and for a
+    request above MAX_TOTAL_SUBSTEPS or -- one kernel per Horner pass, counted over the distinct
+    group substep counts -- MAX_TOTAL_PASSES_ND (``propagate_many``'s budgets)."""
+    steps = [int(s) for s in steps]
+    group = int(group)
+    if group < 1 or not steps or len(steps) % group:
+        raise BlindnoError(f"fp error propagation: {len(steps)} trajectories are not whole groups of {group}")
+    per_group = [max(steps[g * group:(g + 1) * group]) for g in range(len(steps) // group)]
+    worst = max(per_group)
+    intervals = max(0, int(Nsteps) - 1)
+    if worst * max(1, intervals) > MAX_TOTAL_SUBSTEPS:
+        k = int(np.argmax(steps))
+        raise BlindnoError(
+            f"fp error propagation: trajectory {k} needs {worst} Taylor substeps per output interval "
+            f"({worst * intervals} in total, limit {MAX_TOTAL_SUBSTEPS}) -- a force / potential far "
+            f"outside the physical range (e.g. a badly predicted field); refusing to launch")
+    passes = sum(set(per_group)) * intervals * int(degree)
+    if passes > MAX_TOTAL_PASSES_ND:
+        k = int(np.argmax(steps))
+        raise BlindnoError(
+            f"fp error propagation: one kernel per Horner pass, and this request needs {passes} passes "
+            f"({intervals} output intervals x the group substep counts {sorted(set(per_group))} x degree "
+            f"{degree}; limit {MAX_TOTAL_PASSES_ND}); trajectory {k} needs {worst} substeps per interval "
+            f"-- compare fewer or closer times, or check the force / potential; refusing to launch")
+    return [(s, [g for g, sg in enumerate(per_group) if sg == s]) for s in sorted(set(per_group))]
+
+
+def propagate_error_many(sims: Sequence[fokker_planck], initials, tf, Nsteps=None, dt=None, group=None,
+                         normalize=True, device="cuda"):
+    """The squared density error of every trajectory against its group's first one, with no record:
+    (time (Nsteps,), num (B, Nsteps), den (B, Nsteps)) numpy arrays,
+    num[b, o] = sum (p_b(t_o) - p_ref(t_o))^2 and den[b, o] = sum p_ref(t_o)^2 at
+    t = linspace(0, tf, Nsteps).  Trajectories come in consecutive groups of ``group`` (default: the
+    whole batch is one group) whose first member is the reference -- the evaluators' layout, the
+    true field and then one trajectory per model.  Always the grid-resident path
+    (blindno_fp_error_nd: the integrator of blindno_fp_propagate_nd bit for bit, the sums reduced
+    on the device in a fixed order), for grids of any size and dimension; the device holds 3 N
+    doubles of state per trajectory beside its coefficients where ``propagate_many`` holds
+    Nsteps N.  The launches and budgets are ``error_launch_plan``'s."""
+    B = len(sims)
+    if Nsteps is None:
+        Nsteps = int(np.ceil(tf / dt))
+    Nsteps = int(Nsteps)
+    group = B if group is None else int(group)
+    if B == 0 or group < 1 or B % group:
+        raise BlindnoError(f"fp error propagation: {B} trajectories are not whole groups of {group}")
+    dims = sims[0].grid_dims_nd()
+    nx, ny, nz = dims
+    N = nx * ny * nz
+    p0 = np.zeros((B, N))
+    coef = np.zeros((B, 7, N))
+    for k, (sim, ini) in enumerate(zip(sims, initials)):
+        if sim.grid_dims_nd() != dims or sim.ndim != sims[0].ndim:
+            raise BlindnoError("propagate_error_many: every simulator needs the same grid")
+        v = np.asarray(ini(*sim.grid) if callable(ini) else ini, dtype=np.float64).reshape(-1)
+        if normalize:
+            v = v / np.sum(v)
+        p0[k] = v
+        coef[k] = sim.coefficients_nd()
+    time = np.linspace(0, tf, Nsteps)
+    dt_out = tf / (Nsteps - 1) if Nsteps > 1 else 0.0
+    steps = [substeps_for(coef[k], dt_out) if dt_out > 0 else 1 for k in range(B)]
+    plan = error_launch_plan(steps, group, Nsteps)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise BlindnoError("fp propagation runs on a HIP device (there is no CPU path)")
+    err = np.empty((B, Nsteps, 2))
+    for s, groups in plan:
+        ks = [g * group + j for g in groups for j in range(group)]
+        p0_d = torch.from_numpy(np.ascontiguousarray(p0[ks])).to(dev)
+        coef_d = torch.from_numpy(np.ascontiguousarray(coef[ks])).to(dev)
+        err_d = torch.empty(len(ks), Nsteps, 2, dtype=torch.float64, device=dev)
+        scratch = torch.empty(query("blindno_fp_error_nd_scratch_doubles", len(ks), nx, ny, nz),
+                              dtype=torch.float64, device=dev)
+        call("blindno_fp_error_nd", ptr(p0_d), ptr(coef_d), ptr(err_d), ptr(scratch), len(ks), group, nx, ny,
+             nz, Nsteps, s, TAYLOR_DEGREE, float(dt_out), stream_ptr(dev))
+        err[ks] = err_d.cpu().numpy()
+    return time, np.ascontiguousarray(err[..., 0]), np.ascontiguousarray(err[..., 1])

@@ -2,8 +2,8 @@
 compute_time_error.py:361-510 (``compute_time_error``, FPE forces), 1d_FPE/
 compute_time_error.py:215-420 (``compute_time_error_1d``, potential + drag) and 1d_GPE/
 compute_time_error_GPE.py:208-330 (``compute_time_error_gpe``, GPE potentials; its 2D
-and 3D counterparts ``compute_time_error_gpe_2d`` / ``_3d`` are the project's own), each as one
-batched pipeline.
+and 3D counterparts ``compute_time_error_gpe_2d`` / ``_3d`` are the project's own, as is
+``compute_time_error_3d`` for the 3D FPE potential + drag field), each as one batched pipeline.
 
 Per test index the reference normalises the bag with the train statistics, predicts (Fx, Fy)
 with each model, de-normalises, propagates a Gaussian density (centre (-150, -150) nm, width
@@ -371,3 +371,79 @@ def compute_time_error_1d(models: Dict[str, torch.nn.Module], train, test, indic
         for name, arr in out.items():
             np.save(os.path.join(outdir, f"ErrL2_{name}_Nsamples_{len(idx)}.npy"), arr)
     return out
+
+
+# ------------------------------------------------------------------------------- 3D FPE
+KIND_3D = "3d_FPE"
+
+
+def compute_time_error_3d(models: Dict[str, torch.nn.Module], train, test, indices: Iterable[int],
+                          outdir: Optional[str] = None, nsteps: int = 400, tf: float = 2e-4, batch: int = 2,
+                          device="cuda", temperature: float = 300.0, extent_nm: float = 400.0,
+                          resolution_nm: float = 10.0, init_width_nm: float = 50.0) -> List[list]:
+    """The density-trajectory error of the 3d_FPE experiment (the project's own; ``train`` / ``test``
+    are datagen.fpe_3d_dataset npz files or dicts, the defaults its physics): per test index each
+    model predicts (potential, drag field), de-normalised with the train statistics
+    (evaluate.denormalize, kind 3d_FPE); a Gaussian at the origin (width 50 nm) is propagated between
+    reflecting walls under the true fields and under each prediction, the drag as the per-cell field
+    the dataset stores (not its mean).  Every propagation -- the reference and one per model, for
+    every index -- goes through fpe.propagate_error_many with group = 1 + len(models): no density
+    record exists anywhere (at 40^3 x 400 frames it would be 204.8 MB per trajectory), the two sums
+    per frame come back from the device, and ErrL2_density = mean_o sqrt(num_o) / (sqrt(den_o) +
+    1e-12) is ``time_averaged_relative_l2`` of ``compute_time_error``.  A prediction whose drag has
+    a non-positive or non-finite cell cannot be propagated: its ErrL2_density is NaN (its trajectory
+    in the batch is a copy of the reference, so the layout stays whole) and its field errors are
+    still reported (evaluate.rel_l2 against the raw float32 fields, as blindno.evaluate reports
+    them).  Rows [index, model, rel_l2_potential, rel_l2_drag, ErrL2_density] per index, the models
+    in the given order; with ``outdir`` appended to metrics_all.csv."""
+    stats = evaluate.compute_train_stats(KIND_3D, train)
+    data = np.load(test) if isinstance(test, str) else test
+    traj = np.asarray(data["trajectories"])
+    idx = [int(i) for i in indices if 0 <= int(i) < traj.shape[0]]
+    if not idx:
+        return []
+    ngrid = (int(np.ceil(extent_nm / resolution_nm)),) * 3
+    if ngrid != tuple(traj.shape[2:5]):
+        raise fpe.BlindnoError(f"compute_time_error_3d: extent_nm / resolution_nm give a {ngrid} grid, "
+                               f"the data is {tuple(traj.shape[2:5])}")
+    x = torch.tensor(np.stack([evaluate.normalize_input(np.array(traj[i], dtype=np.float32), stats)
+                               for i in idx]), dtype=torch.float32, device=device)
+    grid_t = grid3d(*traj.shape[2:5], device)
+    preds = {name: evaluate.predict(m, x, grid_t, batch).cpu().numpy() for name, m in models.items()}
+
+    def sim(U, drag):
+        U = np.asarray(U, dtype=np.float64)
+        return fpe.fokker_planck(temperature=temperature, drag=np.asarray(drag, dtype=np.float64),
+                                 extent=[extent_nm * NM] * 3, resolution=resolution_nm * NM,
+                                 boundary=fpe.boundary.reflecting, potential=lambda *g: U)
+    sims, fields = [], []
+    for k, i in enumerate(idx):
+        U = np.array(data["potential"][i], dtype=np.float32)
+        drag = np.array(data["drag"][i], dtype=np.float32)
+        ref = sim(U, drag)
+        sims.append(ref)
+        for name in models:
+            pa, pb = evaluate.denormalize(KIND_3D, preds[name][k], stats)
+            ok = bool(np.all(np.isfinite(pb)) and np.all(pb > 0))
+            fields.append((i, name, evaluate.rel_l2(pa, U), evaluate.rel_l2(pb, drag), ok))
+            sims.append(sim(pa, pb) if ok else ref)
+    pdf = fpe.gaussian_pdf(center=(0 * NM, 0 * NM, 0 * NM), width=init_width_nm * NM)
+    per = 1 + len(models)
+    _, num, den = fpe.propagate_error_many(sims, [pdf] * len(sims), tf, Nsteps=nsteps, group=per, device=device)
+    rows = []
+    for k in range(len(idx)):
+        for j in range(len(models)):
+            i, name, rp, rd, ok = fields[k * len(models) + j]
+            b = k * per + 1 + j
+            e = float(np.mean(np.sqrt(num[b]) / (np.sqrt(den[b]) + 1e-12))) if ok else float("nan")
+            rows.append([i, name, rp, rd, e])
+    if outdir is not None:
+        os.makedirs(outdir, exist_ok=True)
+        path = os.path.join(outdir, "metrics_all.csv")
+        header = not os.path.exists(path)
+        with open(path, "a", newline="") as f:
+            w = csv.writer(f)
+            if header:
+                w.writerow(["index", "model", "rel_l2_potential", "rel_l2_drag", "ErrL2_density"])
+            w.writerows(rows)
+    return rows

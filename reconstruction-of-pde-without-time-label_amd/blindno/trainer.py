@@ -21,6 +21,9 @@ Reference loops (one per experiment; the flat module-level scripts):
                                             10, results_nio/
   1d_GPE/train_nio_GPE.py:80-212            NIOFP_schrodinger(1,3,100,25,3,20,40,1), bs 32, lr 1e-3,
                                             eval every 10, results_GPE_nio/
+  the project's own (no reference script): 2d_GPE, and 3d_FPE = NIOFP3D_FNO(2,8,4,2,input_modes=4)
+  on datagen.fpe_3d_dataset files, bs 4, lr 5e-4, eval every 5, results_3d_FPE_fno/ -- an eager
+  step (``Experiment.eager``: no graph capture), one process only, --model fno only
 
 What is kept from the reference, exactly:
   * dataset scaling / z-scoring (``blindno.data``, bit-pinned to the reference classes) and the
@@ -77,6 +80,9 @@ class Experiment:
     # ``fc0`` read through ``.data``; the NIO models train their branch CNN (2d_FPE/train_nio.py:115,
     # 1d_FPE/train_nio.py:96: Adam(model.parameters())), so only fc0 is excluded there
     exclude_prefixes: Sequence[str] = ("branch.", "fc0.")
+    # no GraphedBagStep: every batch runs the eager step the partial last batch takes (the 3D
+    # models, whose step has no graph capture; one process only)
+    eager: bool = False
 
 
 def _experiments(model: str = "fno"):
@@ -147,6 +153,12 @@ def _experiments(model: str = "fno"):
                              lambda n, dev: nio.NIOFP2D_FNO(2, 3, 100, 25, 3, 12, 32, 1, heads=("fno_V",),
                                                             branch_last_kernel=Encoder2D.kernel_for_grid(n)),
                              5e-4, 4, 5, "results_2d_GPE_fno", False),
+        # the project's own 3D experiment (datagen.fpe_3d_dataset): the benched NIOFP3D_FNO
+        # configuration (profiles/nio3d_fno_bench.json) with the 2D FPE loop, metric and loss files;
+        # the step is eager (7.2 ms at 40^3: launch overhead is not what limits it); NIO-FNO only
+        "3d_FPE": Experiment("3d_FPE", 3, data.TrajectoryDataset3D,
+                             lambda n, dev: nio.NIOFP3D_FNO(2, 8, 4, 2, dev, input_modes=4), 5e-4, 4, 5,
+                             "results_3d_FPE_fno", True, all4, ("fc0.",), eager=True),
     }
 
 
@@ -168,6 +180,7 @@ class Trainer:
         from . import data as bdata
         from .train import (DataParallel, FlatAdam, GraphedBagStep, StepLR, grid1d, grid2d,
                             trained_parameters)
+        from .timeerror import grid3d
         from .nio import draw_bag
         from . import load_library, mse_loss
         load_library()
@@ -175,6 +188,9 @@ class Trainer:
         self.seed = seed
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         self.rank = dist.get_rank() if self.world > 1 else 0
+        if exp.eager and self.world > 1:
+            raise ValueError(f"experiment {exp.name} runs an eager step, which has no data-parallel path: "
+                             f"run it in one process (world size {self.world})")
         self.outdir = outdir
         self.save_interval = save_interval or exp.save_interval
         self.B = batch or exp.batch
@@ -190,7 +206,10 @@ class Trainer:
         self.Xtr, self.Ytr, self.Xte, self.Yte = Xtr, Ytr, Xte, Yte
         self.T = Xtr.shape[1]
         n = Xtr.shape[2]
-        self.grid = grid2d(n, Xtr.shape[3], device) if exp.dim == 2 else grid1d(n, device)
+        if exp.dim == 3:
+            self.grid = grid3d(n, Xtr.shape[3], Xtr.shape[4], device)
+        else:
+            self.grid = grid2d(n, Xtr.shape[3], device) if exp.dim == 2 else grid1d(n, device)
         # seeds after the split, as the reference (2d_FPE/train_fno.py:78-81)
         np.random.seed(seed + self.rank)
         torch.manual_seed(seed + self.rank)
@@ -203,7 +222,8 @@ class Trainer:
         self.sched = StepLR(self.opt, 100, 0.5, world_steps=world_steps)
         self.xb = torch.empty((self.B,) + tuple(Xtr.shape[1:]), device=device)
         self.yb = torch.empty((self.B,) + tuple(Ytr.shape[1:]), device=device)
-        self.graphed = GraphedBagStep(self.model, mse_loss, self.opt, self.dp, self.xb, self.yb, self.grid)
+        self.graphed = None if exp.eager else \
+            GraphedBagStep(self.model, mse_loss, self.opt, self.dp, self.xb, self.yb, self.grid)
         self.loss_sum = torch.zeros((), dtype=torch.float64, device=device)
         self.history = {k: [] for k in exp.loss_files}
         self.best = math.inf
@@ -233,12 +253,12 @@ class Trainer:
             ids = ids.to(self.device)
             b = ids.numel()
             _, idx = self.draw_bag(self.T)                # the reference's numpy draw
-            if b == self.B:
+            if b == self.B and self.graphed is not None:
                 torch.index_select(self.Xtr, 0, ids, out=self.xb)
                 torch.index_select(self.Ytr, 0, ids, out=self.yb)
                 key = self.graphed.step(idx)
                 self.loss_sum.add_(self.graphed.loss[key], alpha=float(b))
-            else:                                         # partial last batch (one process)
+            else:                                         # partial last batch, eager experiment (one process)
                 out = self.model(self.Xtr.index_select(0, ids), self.grid, bag_idx=idx)
                 loss = self.mse_loss(out, self.Ytr.index_select(0, ids))
                 loss.backward()

@@ -139,3 +139,137 @@ BLINDNO_API int blindno_fp_propagate_nd(const double* p0, const double* coef, do
 #undef PASS
   return (int)hipGetLastError();
 }
+
+// ---- blindno_fp_error_nd (include/blindno_fpe_err.h): the same propagation with no record.
+//
+// A density-error evaluation wants two numbers per trajectory and frame, |p - p_ref|^2 and
+// |p_ref|^2, not the frames: at 40^3 x 400 frames the record is 204.8 MB per trajectory against
+// 1.5 MB of state.  Here the density lives in scratch beside the two iterates, the passes are
+// fp_nd_pass_kernel's in blindno_fp_propagate_nd's order (so every iterate has the record's bits),
+// and after the initial state and after every output interval two small launches reduce the sums:
+//   stage one  one workgroup per (trajectory, tile of 256 cells): each lane squares its cell, the
+//              wave sums by a fixed shuffle tree (offsets 32, 16 .. 1), lane 0 of the four waves
+//              meet in LDS and thread 0 adds them in wave order -> partial (B, tiles, 2)
+//   stage two  one workgroup per trajectory: thread t adds tiles t, t + 256, .. in index order,
+//              then the same tree -> err (B, nout, 2)
+// Every addition has a fixed place, so a second call repeats the bits, and a trajectory reads only
+// its own group's cells, so the rest of the batch cannot change them.  Trajectory b's reference is
+// trajectory (b / group) * group; for the reference itself p - p_ref is 0.0 in every cell.
+namespace {
+
+// sum over the workgroup of (a, b), valid in thread 0; `red` is 2 x 4 doubles of LDS
+__device__ __forceinline__ void fp_nd_block_sum2(double& a, double& b, double (*red)[kTile / 64]) {
+  for (int off = 32; off > 0; off >>= 1) {
+    a += __shfl_down(a, off, 64);
+    b += __shfl_down(b, off, 64);
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[0][wave] = a;
+    red[1][wave] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a = red[0][0];
+    b = red[1][0];
+    for (int w = 1; w < kTile / 64; ++w) {
+      a += red[0][w];
+      b += red[1][w];
+    }
+  }
+}
+
+__global__ __launch_bounds__(kTile) void fp_nd_err_tile_kernel(const double* __restrict__ p,
+                                                               double* __restrict__ partial, int N,
+                                                               int tiles, int group) {
+  __shared__ double red[2][kTile / 64];
+  const int b = blockIdx.x / tiles;
+  const int i = (blockIdx.x - b * tiles) * kTile + threadIdx.x;
+  double num = 0.0, den = 0.0;
+  if (i < N) {
+    const double r = p[(int64_t)(b / group * group) * N + i];
+    const double d = p[(int64_t)b * N + i] - r;
+    num = d * d;
+    den = r * r;
+  }
+  fp_nd_block_sum2(num, den, red);
+  if (threadIdx.x == 0) {
+    partial[2 * (int64_t)blockIdx.x] = num;
+    partial[2 * (int64_t)blockIdx.x + 1] = den;
+  }
+}
+
+__global__ __launch_bounds__(kTile) void fp_nd_err_sum_kernel(const double* __restrict__ partial,
+                                                              double* __restrict__ err, int tiles,
+                                                              int nout, int o) {
+  __shared__ double red[2][kTile / 64];
+  const int b = blockIdx.x;
+  const double* pt = partial + 2 * (int64_t)b * tiles;
+  double num = 0.0, den = 0.0;
+  for (int t = threadIdx.x; t < tiles; t += kTile) {
+    num += pt[2 * (int64_t)t];
+    den += pt[2 * (int64_t)t + 1];
+  }
+  fp_nd_block_sum2(num, den, red);
+  if (threadIdx.x == 0) {
+    double* e = err + 2 * ((int64_t)b * nout + o);
+    e[0] = num;
+    e[1] = den;
+  }
+}
+
+}  // namespace
+
+BLINDNO_API int64_t blindno_fp_error_nd_scratch_doubles(int B, int nx, int ny, int nz) {
+  int64_t N, blocks;
+  if (!fp_nd_cells(B, nx, ny, nz, &N, &blocks)) return -1;
+  return 3 * (int64_t)B * N + 2 * blocks;      // p, the two iterates, the tile partials
+}
+
+BLINDNO_API int blindno_fp_error_nd(const double* p0, const double* coef, double* err,
+                                    double* scratch, int B, int group, int nx, int ny, int nz,
+                                    int nout, int substeps, int degree, double dt_out,
+                                    void* stream) {
+  int64_t N, blocks;
+  if (!fp_nd_cells(B, nx, ny, nz, &N, &blocks) || group < 1 || B % group != 0 || nout < 1 ||
+      substeps < 1 || degree < 1 || !p0 || !coef || !err || !scratch)
+    return (int)hipErrorInvalidValue;
+  hipStream_t st = (hipStream_t)stream;
+  const int tiles = (int)((N + kTile - 1) / kTile);
+  const int grid = (int)blocks;
+  const double h = dt_out / substeps;
+  const int64_t BN = (int64_t)B * N;
+  double* p = scratch;                         // the density; with degree 1 it rotates through all three
+  double* wa = scratch + BN;
+  double* wb = scratch + 2 * BN;
+  double* partial = scratch + 3 * BN;          // (B, tiles, 2)
+  fp_nd_copy_kernel<<<grid, kTile, 0, st>>>(p0, p, N, (int)N, tiles);
+#define PASS(P_, WI_, WO_, K_)                                                                  \
+  fp_nd_pass_kernel<<<grid, kTile, 0, st>>>(coef, P_, N, WI_, N, WO_, N, (int)N, nx, ny, nz, tiles, \
+                                            h, K_)
+  for (int o = 0; o < nout; ++o) {
+    for (int sub = 0; o > 0 && sub < substeps; ++sub) {
+      if (degree == 1) {
+        // the single pass reads its neighbours from p itself: write the next density elsewhere
+        PASS(p, p, wa, 1);
+        double* t = p;
+        p = wa;
+        wa = t;
+        continue;
+      }
+      const double* wi = p;
+      double* wo = wa;
+      for (int k = degree; k >= 2; --k) {
+        PASS(p, wi, wo, k);
+        wi = wo;
+        wo = wo == wa ? wb : wa;
+      }
+      // last pass: each cell reads its own p and writes its own cell of p
+      PASS(p, wi, p, 1);
+    }
+    fp_nd_err_tile_kernel<<<grid, kTile, 0, st>>>(p, partial, (int)N, tiles, group);
+    fp_nd_err_sum_kernel<<<B, kTile, 0, st>>>(partial, err, tiles, nout, o);
+  }
+#undef PASS
+  return (int)hipGetLastError();
+}

@@ -195,7 +195,8 @@ int blindno_rowidft_epi_crop(const float* Z, const float* x, const float* wc, co
 /* Adjoint of rowidft_epi w.r.t. its input field:
  *   dx[n,i,h,w] = sum_k Re(G[n,h,k,i] e^{+2pi i k w/P2}) + sum_o Wc[o,i] dz[n,o,h,w]
  * then, if act == 1, dx *= GELU'(xsrc[n,i,h,w]) (xsrc = the layer input's pre-activation).
- * wc == NULL drops the conv term.  tb as in blindno_rowidft_epi.
+ * wc == NULL drops the conv term (the bare transform's adjoint: dz and xsrc are unused, and
+ * act must be 0 -- act == 1 without wc is refused).  tb as in blindno_rowidft_epi.
  * If partial != NULL (requires C <= 4 and wc), the 1x1-conv gradients are reduced in the same
  * pass into partial[blindno_rowidft_bwd_nchunk(...)][C*C + C]
  * = [dWc[o][i] = sum dz_o f(xsrc_i) | dbc[o] = sum dz_o]. */

@@ -62,9 +62,11 @@ __global__ __launch_bounds__(256) void rowinv_mfma_kernel(
     const float* __restrict__ Z, const float* __restrict__ xs, const float* __restrict__ dz,
     const float* __restrict__ wc, const float* __restrict__ bc, float* __restrict__ out,
     const float* __restrict__ TB, float* __restrict__ partial, int Bn, int C, int P1, int P2,
-    int m2, int TPW, BagLift bl, int Bg, int64_t wgs, int dN1, int dN2) {
+    int m2, int TPW, BagLift bl, int Bg, int64_t wgs, int dN1, int dN2, int tiled) {
   // MODE 1: dz is read only on its valid region h < dN1, w < dN2 (zero elsewhere: the gradient
   // of a cropped FNO output; see rowdft_mfma_kernel)
+  // tiled: Z is in A-tile order (rowinv_tile_layout; a cropped dz sends such a shape here
+  // instead of to rowinv_wide_kernel): rows and channels in whole groups of 4, m2 even
   extern __shared__ float sTB[];                    // [KS][NT][64] when LDSB
   const int KS = (m2 + 1) >> 1;
   const int NT = (P2 + 15) >> 4;
@@ -97,12 +99,17 @@ __global__ __launch_bounds__(256) void rowinv_mfma_kernel(
     const int ra = 4 * quad + (c16 >> 2), ca = c0 + (c16 & 3);
     const bool aok = ra < nrows && ca < C;
     const float* zrow = Z + ((int64_t)(aok ? ra : 0) * m2) * C * 2;
+    // tile order: this lane's element of K step s is Zt[((quad NG + g) KS + s) 64 + lane]
+    const float* ztile = Z + ((int64_t)qg * KS) * 64 + lane;
     float av[KSM];                                  // A operand, reused by every column tile
 #pragma unroll
     for (int s = 0; s < KSM; ++s) {
       const int kk = 4 * s + g4;                    // K index supplied by this lane
       const int k = kk >> 1;
-      av[s] = (aok && s < KS && k < m2) ? zrow[(k * C + ca) * 2 + (kk & 1)] : 0.f;
+      if (tiled)
+        av[s] = s < KS ? ztile[s * 64] : 0.f;
+      else
+        av[s] = (aok && s < KS && k < m2) ? zrow[(k * C + ca) * 2 + (kk & 1)] : 0.f;
     }
     // this lane's output point: row R0 + g4, column 16 tile + c16, channels c0 + r
     const int ro = 4 * quad + g4;
@@ -1190,6 +1197,8 @@ int rowinv_launch(const float* Z, const float* xs, const float* dz, const float*
   if (G == 1) wgs = 0;
   if (Bn <= 0 || C <= 0 || C > 32 || m2 <= 0 || P2 <= 0) return (int)hipErrorInvalidValue;
   if (WG && C > 4) return (int)hipErrorInvalidValue;
+  // the adjoint's GELU' factor belongs to the layer epilogue: the bare transform (no conv) has none
+  if (MODE == 1 && ACT && !wc) return (int)hipErrorInvalidValue;
   const int64_t zel = (int64_t)Bn * P1 * m2 * C * 2, fel = (int64_t)Bn * C * P1 * P2;
   if (zel >= INT32_MAX || fel >= ((int64_t)1 << 40)) return (int)hipErrorInvalidValue;
   const int cm = C <= 4 ? 4 : (C <= 8 ? 8 : (C <= 16 ? 16 : 32));
@@ -1325,16 +1334,19 @@ int rowinv_launch(const float* Z, const float* xs, const float* dz, const float*
   }
   // the next layer's row DFT otherwise runs as its own launch after this one
   if (rd.At && (G != 1 || (MODE == 1 && LIFT))) return (int)hipErrorInvalidValue;
+  // a tile-layout shape whose dz is cropped (the wide kernel takes full fields only): the
+  // general kernel reads the spectrum in the order the column pass wrote it
+  const int tiled = rowinv_tile_layout(Bn, C, P1, P2, m2) ? 1 : 0;
 #define RI(CM_, KS_)                                                                         \
   do {                                                                                       \
     if (g.ldsb)                                                                              \
       rowinv_mfma_kernel<CM_, KS_, MODE, ACT, WG, 1, LIFT><<<nblocks, 256, sh, st>>>(        \
           Z, xs, dz, wc, bc, out, TB, partial, Bn, C, P1, P2, m2, g.TPW, bl, Bg, wgs, dN1,   \
-          dN2);                                                                              \
+          dN2, tiled);                                                                       \
     else                                                                                     \
       rowinv_mfma_kernel<CM_, KS_, MODE, ACT, WG, 0, LIFT><<<nblocks, 256, sh, st>>>(        \
           Z, xs, dz, wc, bc, out, TB, partial, Bn, C, P1, P2, m2, g.TPW, bl, Bg, wgs, dN1,   \
-          dN2);                                                                              \
+          dN2, tiled);                                                                       \
   } while (0)
 #define RI_K(CM_) \
   if (ks <= 8) RI(CM_, 8); else if (ks <= 16) RI(CM_, 16); else RI(CM_, 24);

@@ -319,7 +319,9 @@ int blindno_colmix(const float* part, int nbv, const float* Wt, float* Xsave, fl
                    const float* Dg2, blindno_stream_t stream);
 /* row inverses with Z built from Y (ZY) and, with part != NULL, the next row DFT as column-DFT
  * partials (CD): counterparts of blindno_rowidft_epi(_crop / _rd), _epi_lift_rd, _bwd_rd /
- * _bwd_crop and _bwd_lift.  Tp: the next row DFT's image (blindno_rowdft's). */
+ * _bwd_crop and _bwd_lift.  Tp: the next row DFT's image (blindno_rowdft's).  These run in the
+ * transposed C = 4 kernel only: 16-byte aligned bases and a crop width (oN2, dN2, N2, Wo) in whole
+ * float4s, anything else is hipErrorInvalidValue. */
 int blindno_rowidft_epi_zc(const float* Y, const float* x, const float* wc, const float* bc, float* z,
                            const float* tb, const float* tab, float* part, const float* Tp, int Bn,
                            int C, int P1, int P2, int m1, int m2, int act, int act_next, int oN1,

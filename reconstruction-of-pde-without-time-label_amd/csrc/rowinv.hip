@@ -1290,6 +1290,10 @@ int rowinv_launch(const float* Z, const float* xs, const float* dz, const float*
       return (int)hipGetLastError();
     }
   }
+  // the folded column pass (Z == NULL, Y in sc) exists only in the transposed kernel: a launch-time
+  // gate that failed (crop width not in whole float4s, unaligned base) is refused, not sent on to
+  // the general kernel, which would read Z
+  if (ZC) return (int)hipErrorInvalidValue;
   // the general kernel's own geometry also where the shape suits rowfuse but a launch-time gate
   // (G, alignment, crop width) sent it here; nblocks stays the caller's (it sized the partials,
   // and the persistent general kernel strides its items over any grid)

@@ -102,6 +102,119 @@ def test_chained_layer_cd_matches_rowdft(Bn, N):
     assert e <= 1e-6, e
 
 
+# ------------------------------------------------------------------ dz = lw_l ghat v formed on load
+def _bag_dz_setup(crop, weighted):
+    """The smallest folded-pass geometry (C 4, m 12, P 32; B 2 bags of U 3 snapshots): v from
+    blindno_project_bag_fwd, dz = lw ghat v written by blindno_project_bag_bwd."""
+    from blindno import ops
+    from blindno._lib import call, ptr, query, stream_ptr
+    B, U, C, m, P = 2, 3, 4, 12, 32
+    Ho, Wo = crop
+    Bn = B * U
+    assert query("blindno_colspec_ok", Bn, C, P, P, m, m) == 1
+    assert query("blindno_colspec_ok", Bn, C, 16, 32, m, m) == 0          # nothing smaller is accepted
+    g = torch.Generator(device="cuda").manual_seed(300 + Wo)
+    r = lambda *s, scale=1.0: torch.randn(*s, device="cuda", generator=g) * scale
+    z, w1, b1, w2, b2 = r(Bn, C, P, P), r(128, C, scale=0.4), r(128, scale=0.1), r(1, 128, scale=0.1), r(1)
+    ghat = r(B, Ho * Wo)
+    lw = None
+    if weighted:
+        lw = torch.tensor([2.0, 1.0, 3.0], device="cuda") / 6.0
+    ubar = torch.empty(B, Ho * Wo, device="cuda")
+    stats = torch.empty(query("blindno_project_bag_stats_floats", B, Ho, Wo), device="cuda")
+    v = torch.full_like(z, float("nan"))
+    call("blindno_project_bag_fwd", ptr(z), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(lw), ptr(ubar), ptr(stats),
+         ptr(v), B, U, C, P, P, Ho, Wo, 128, stream_ptr())
+    dz = torch.full_like(z, float("nan"))                                 # never read outside the crop
+    partial = torch.empty(3, 128 * C + 257, device="cuda")
+    call("blindno_project_bag_bwd", ptr(stats), ptr(ghat), ptr(w2), ptr(lw), ptr(v), ptr(dz), ptr(partial), 3, B, U,
+         C, P, P, Ho, Wo, 128, stream_ptr())
+    cs = ops._ColSpec(Bn, C, P, P, m, m, z.device)
+    return cs, v, dz, ghat, lw, (B, U, C, m, P, Bn)
+
+
+@pytest.mark.parametrize("weighted", [False, True], ids=["lw_null", "lw_given"])
+@pytest.mark.parametrize("crop", [(23, 29), (23, 28)], ids=["wo29", "wo28_float4"])
+def test_rowdft_cd_bag_matches_rowdft_cd_of_dz(crop, weighted):
+    """blindno_rowdft_cd_bag(v, ghat, lw) vs blindno_rowdft_cd(dz, act 0, Ho, Wo): both form
+    fl(fl(lw ghat) v) before the same accumulation, so the partials are bit-identical."""
+    from blindno._lib import call, ptr, stream_ptr
+    cs, v, dz, ghat, lw, (B, U, C, m, P, Bn) = _bag_dz_setup(crop, weighted)
+    pa, pb = (torch.full_like(cs.part(C, v), -12345.678) for _ in range(2))
+    call("blindno_rowdft_cd", ptr(dz), ptr(pa), ptr(cs.Tp), ptr(cs.tab), Bn, C, P, P, m, 0, crop[0], crop[1],
+         stream_ptr())
+    call("blindno_rowdft_cd_bag", ptr(v), ptr(ghat), ptr(lw), U, ptr(pb), ptr(cs.Tp), ptr(cs.tab), Bn, C, P, P, m,
+         crop[0], crop[1], stream_ptr())
+    torch.cuda.synchronize()
+    assert torch.isfinite(pa).all() and bool((pa != -12345.678).any())
+    assert torch.equal(pa, pb)
+
+
+@pytest.mark.parametrize("weighted", [False, True], ids=["lw_null", "lw_given"])
+@pytest.mark.parametrize("crop", [(23, 29), (23, 28)], ids=["wo29", "wo28_float4"])
+def test_rowidft_bwd_zc_bag_matches_rowidft_bwd_zc_of_dz(crop, weighted):
+    """blindno_rowidft_bwd_zc_bag(Yb, v, ghat, lw) vs blindno_rowidft_bwd_zc(Yb, dz, act 1, Ho, Wo)
+    (they may take different instantiations): dx and the column-DFT partials to 1e-6 rel-L2, the
+    reduced dWc | dbc to 1e-5; dx also per element against spectral_stage_ref.row_inv_adj on
+    Z[n,h,k,c] = sum_j Yb[n,k,c,j] e^{+2 pi i r_j h / P1} under that file's bound with the chain
+    n = K1 (column inverse) + 2 m2 (row inverse) + C (conv) + 1 (the GELU' product)."""
+    import spectral_stage_ref as sr
+    from blindno import ops
+    from blindno._lib import call, ptr, query, stream_ptr
+    cs, v, dz, ghat, lw, (B, U, C, m, P, Bn) = _bag_dz_setup(crop, weighted)
+    g = torch.Generator(device="cuda").manual_seed(17)
+    Yb = torch.randn(Bn, m, C, cs.K1, 2, device="cuda", generator=g) * 0.1
+    cw = torch.randn(C, C, device="cuda", generator=g) / C
+    xsrc = torch.randn(Bn, C, P, P, device="cuda", generator=g)
+    nchunk = query("blindno_colspec_bwd_nchunk", Bn, P)
+    if crop[1] % 4:
+        # the folded adjoint runs in the transposed kernel only, whose field accesses are whole
+        # float4s: both entries refuse the width on the host and write nothing (before the refusal
+        # blindno_rowidft_bwd_zc went on to the general row inverse with Z == NULL)
+        from blindno._lib import load
+        dx = torch.full((Bn * C * P * P + 128,), -12345.678, device="cuda")
+        part = torch.zeros_like(cs.part(C, v))
+        pw = torch.zeros(nchunk, C * C + C, device="cuda")
+        tail = (ptr(cw), ptr(xsrc), ptr(dx[64:]), ptr(cs.tb), ptr(cs.tab), ptr(part), ptr(cs.Tp), ptr(pw), Bn, C, P, P,
+                m, m, 1, crop[0], crop[1], stream_ptr())
+        assert int(load().blindno_rowidft_bwd_zc(ptr(Yb), ptr(dz), *tail)) == 1
+        assert int(load().blindno_rowidft_bwd_zc_bag(ptr(Yb), ptr(v), ptr(ghat), ptr(lw), U, *tail)) == 1
+        torch.cuda.synchronize()
+        assert bool((dx == -12345.678).all()) and not part.any() and not pw.any()
+        return
+    res = []
+    for bag in (False, True):
+        dx = torch.full((Bn, C, P, P), float("nan"), device="cuda")
+        part = torch.zeros_like(cs.part(C, v))
+        pw = torch.full((nchunk, C * C + C), float("nan"), device="cuda")
+        tail = (ptr(cw), ptr(xsrc), ptr(dx), ptr(cs.tb), ptr(cs.tab), ptr(part), ptr(cs.Tp), ptr(pw), Bn, C, P, P, m,
+                m, 1, crop[0], crop[1], stream_ptr())
+        if bag:
+            call("blindno_rowidft_bwd_zc_bag", ptr(Yb), ptr(v), ptr(ghat), ptr(lw), U, *tail)
+        else:
+            call("blindno_rowidft_bwd_zc", ptr(Yb), ptr(dz), *tail)
+        gw = ops.reduce_partials(pw, nchunk, C * C + C)
+        torch.cuda.synchronize()
+        res.append((dx.cpu().numpy(), part.cpu().numpy(), gw.cpu().numpy()))
+    (dx0, p0, g0), (dx1, p1, g1) = res
+    e = (rel_l2(dx1, dx0), rel_l2(p1, p0), rel_l2(g1, g0))
+    print(f"crop={crop} weighted={weighted}: dx {e[0]:.2e}, partials {e[1]:.2e}, dWc|dbc {e[2]:.2e}")
+    assert np.isfinite(dx1).all() and e[0] <= 1e-6 and e[1] <= 1e-6 and e[2] <= 1e-5, e
+    # per element against float64
+    Y = sr.cplx(Yb.cpu().numpy())
+    F = sr._phase(np.arange(P), sr.kept_rows(m, P), P, -1.0)
+    G = np.einsum("nkcj,hj->nhkc", Y, np.conj(F), optimize=True)
+    Gabs = np.repeat(np.abs(Y).sum(-1).transpose(0, 1, 2)[:, None], P, 1)            # (Bn, P1, m2, C)
+    dzn, wc, xs = dz.cpu().numpy().astype(np.float64), cw.cpu().numpy().astype(np.float64), xsrc.cpu().numpy()
+    ref = sr.row_inv_adj(G, P, dzn, wc, xs, 1, crop)
+    S, gwt = sr.row_inv_adj_abs(None, P, dzn, wc, xs, 1, crop, bare=sr.row_inv_bare_abs(Gabs, P))
+    bound = (cs.K1 + 2 * m + C + 1 + 8) * sr.U24 * S + sr.GELU_ABS * gwt
+    for name, dx in (("zc", dx0), ("zc_bag", dx1)):
+        r = sr.worst(np.abs(dx.astype(np.float64) - ref), bound)
+        print(f"   dx ({name}) vs float64: worst err/bound {r:.3f}")
+        assert r <= 1.0, (name, r)
+
+
 @pytest.mark.parametrize("N,B,dedup", [(128, 2, True), (128, 3, False), (256, 1, True)])
 def test_encoder_colspec_matches_colpass(N, B, dedup):
     """NIOFP2D_FNO's snapshot encoder (ops.BagEncoderFn, 2 layers, modes 12, width 4) with the

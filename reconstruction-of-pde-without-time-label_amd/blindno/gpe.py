@@ -1,7 +1,8 @@
 """Gross-Pitaevskii data generators / density propagators and the density-error metrics on the
 GPU, fp64 like the reference: 1D (libblindno ``blindno_gpe_solve`` / ``blindno_trapz_rows``) and
 2D (``blindno_gpe2d_solve`` / ``blindno_trapz2_frames``, the ``*_2d`` functions) and 3D
-(``blindno_gpe3d_solve`` / ``blindno_trapz3_frames``, the ``*_3d`` functions at the end).
+(``blindno_gpe3d_solve`` / ``blindno_trapz3_frames``, the ``*_3d`` functions at the end, with the
+record-free ``solve_error_batch_3d`` on ``blindno_gpe3d_error``).
 
 Reference (yl602019618/Reconstruction-of-PDE-without-Time-Label):
   get_initial_condition, solve_GPE_custom, generate_and_save_training_data
@@ -507,7 +508,95 @@ def time_averaged_L2_error_3d(time_ref, rho_ref, time_pred, rho_pred, grid, eps:
     s = torch.empty(nt, 2, dtype=F64, device=dev)
     call("blindno_trapz3_frames", ptr(a), ptr(b), ptr(d64(xg)), ptr(d64(yg)), ptr(d64(zg)), ptr(s), nt, nx, ny, nz,
          stream_ptr(dev))
-    rel = s[:, 0].clamp_min(0).sqrt() / (s[:, 1].clamp_min(0).sqrt() + eps)
-    t = d64(time_ref)
+    return time_averaged_L2_error_from_sums(d64(time_ref), s[:, 0], s[:, 1], eps)
+
+
+def time_averaged_L2_error_from_sums(t, num, den, eps: float = 1e-12) -> float:
+    """The end of ``time_averaged_L2_error_3d``, shared with the record-free path: from the per-time
+    integrals num = trapz((rho_pred - rho_ref)^2) and den = trapz(rho_ref^2), (Nt,) each,
+    rel = sqrt(max(num, 0)) / (sqrt(max(den, 0)) + eps), then the trapezoid time average of rel over
+    ``t`` divided by (t_end - t_0).  ``num`` / ``den`` are fp64 tensors (on any device) or arrays;
+    ``t`` is brought to their device."""
+    num = num if torch.is_tensor(num) else torch.from_numpy(np.asarray(num, dtype=np.float64))
+    den = den if torch.is_tensor(den) else torch.from_numpy(np.asarray(den, dtype=np.float64))
+    t = t if torch.is_tensor(t) else torch.from_numpy(np.asarray(t, dtype=np.float64))
+    t = t.to(num.device, F64)
+    rel = num.clamp_min(0).sqrt() / (den.clamp_min(0).sqrt() + eps)
     integral = (0.5 * (rel[:-1] + rel[1:]) * (t[1:] - t[:-1])).sum()
     return float(integral / (t[-1] - t[0]))
+
+
+def solve_error_batch_3d(psi0, x, y, z, dt: float, t_final: float, order: int, g, kappa, V,
+                         group: Optional[int] = None, rec_every: int = 1, device=None):
+    """``solve_batch_3d`` without a record (blindno_gpe3d_error): the same B trajectories, integrated
+    by the same launch sequence, but of every ``rec_every``-th step only the two integrals
+    ``time_averaged_L2_error_3d`` needs come back.  Trajectories come in consecutive groups of
+    ``group`` (default: the whole batch) whose first member is the group's reference.
+
+    psi0, x, y, z, dt, t_final, order, g, kappa, V: as in ``solve_batch_3d``.  Returns a dict with
+    ``t`` (numpy, the recorded times) and the fp64 device tensors ``num`` (B, nrec) =
+    trapz_z trapz_y trapz_x (|psi_b| - |psi_ref(b)|)^2 and ``den`` (B, nrec) = the same integral of
+    |psi_ref(b)|^2; ``num`` of a reference is exactly 0.  The device holds three doubles per cell and
+    trajectory whatever nrec is (the working field and one |psi| frame), plus two per 1024 cells.
+
+    Refused before anything is launched (BlindnoError): a batch that is not whole groups, more than
+    MAX_LAUNCHES_3D kernel launches (blindno_gpe3d_error_launches: the solver's plus two per recorded
+    step), scratch above MAX_RECORD_BYTES, and whatever blindno_gpe3d_error refuses."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    z = np.asarray(z, dtype=np.float64)
+    shape = (len(x), len(y), len(z))
+    nx, ny, nz = shape
+    V = np.asarray(V, dtype=np.float64)
+    if V.ndim == 3:
+        V = V[None]
+    if V.ndim != 4 or V.shape[1:] != shape:
+        raise BlindnoError(f"V has shape {V.shape}; expected (B, {nx}, {ny}, {nz}) or ({nx}, {ny}, {nz})")
+    B = V.shape[0]
+    psi0 = np.asarray(psi0, dtype=np.complex128)
+    batched = psi0.ndim == 4
+    if psi0.shape[-3:] != shape or psi0.ndim not in (3, 4):
+        raise BlindnoError(f"psi0 has shape {psi0.shape}; expected (B, {nx}, {ny}, {nz}) or ({nx}, {ny}, {nz})")
+    if batched and psi0.shape[0] != B:
+        raise BlindnoError("psi0 and V batch sizes differ")
+    g = np.broadcast_to(np.asarray(g, dtype=np.float64), (B,)).copy()
+    kappa = np.broadcast_to(np.asarray(kappa, dtype=np.float64), (B,)).copy()
+    for name, n in (("Nx", nx), ("Ny", ny), ("Nz", nz)):
+        if n & (n - 1) or n < 4 or n > 1024:
+            raise BlindnoError(f"{name} = {n}: the 3D solver needs a power of two in [4, 1024]")
+    if nx * ny * nz > 1 << 24:
+        raise BlindnoError(f"{nx} x {ny} x {nz} cells: the 3D solver takes at most 2^24 per trajectory")
+    if order not in (2, 4):
+        raise BlindnoError(f"order = {order}: the solver has orders 2 and 4")
+    if int(rec_every) < 1:
+        raise BlindnoError(f"rec_every = {rec_every}: must be at least 1")
+    group = B if group is None else int(group)
+    if group < 1 or B % group:
+        raise BlindnoError(f"{B} trajectories are not whole groups of {group}")
+    nt = int(t_final / dt) + 1
+    nsteps = nt - 1
+    nrec = nsteps // int(rec_every) + 1
+    launches = query("blindno_gpe3d_error_launches", nsteps, int(order), int(rec_every))
+    if launches > MAX_LAUNCHES_3D:
+        raise BlindnoError(
+            f"{nsteps} steps of order {order} with {nrec} reduced frames are {launches} kernel launches (limit "
+            f"MAX_LAUNCHES_3D = {MAX_LAUNCHES_3D}); refusing to launch -- raise rec_every or shorten t_final")
+    doubles = query("blindno_gpe3d_error_scratch_doubles", B, nx, ny, nz)
+    if 8 * doubles > MAX_RECORD_BYTES:
+        raise BlindnoError(
+            f"the scratch of {B} trajectories x {nx} x {ny} x {nz} is {8 * doubles} bytes (limit MAX_RECORD_BYTES = "
+            f"{MAX_RECORD_BYTES}); refusing to launch -- solve fewer groups per call")
+    dev = _dev(device)
+    t_full = np.linspace(0, t_final, nt)
+    # fresh C-ordered copies: the inputs may be read-only or broadcast views
+    p0 = torch.from_numpy(np.array(psi0, order="C").view(np.float64)).to(dev)
+    Vd = torch.from_numpy(np.array(V, order="C")).to(dev)
+    gd = torch.from_numpy(g).to(dev)
+    kd = torch.from_numpy(kappa).to(dev)
+    xd, yd, zd = (torch.from_numpy(np.array(a)).to(dev) for a in (x, y, z))
+    err = torch.empty(B, nrec, 2, dtype=F64, device=dev)
+    scratch = torch.empty(doubles, dtype=F64, device=dev)
+    call("blindno_gpe3d_error", ptr(p0), ptr(Vd), ptr(gd), ptr(kd), ptr(xd), ptr(yd), ptr(zd),
+         float(x[1] - x[0]), float(y[1] - y[0]), float(z[1] - z[0]), float(dt), nsteps, int(order), int(rec_every),
+         group, ptr(err), ptr(scratch), B, nx, ny, nz, int(batched), stream_ptr(dev))
+    return {"t": t_full[::rec_every][:nrec], "num": err[:, :, 0], "den": err[:, :, 1]}

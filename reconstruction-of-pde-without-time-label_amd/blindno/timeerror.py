@@ -227,10 +227,34 @@ def grid3d(nx: int, ny: int, nz: int, device) -> torch.Tensor:
     return torch.tensor(np.stack(g, axis=3), device=device)
 
 
+def _gpe_3d_errors_record_free(psi0, grids, dt, t_final, order, g, kappa, V, per, rec_every, device) -> List[float]:
+    """time_averaged_L2_error_3d of every trajectory against its group's first (groups of ``per``
+    consecutive trajectories), through blindno.gpe.solve_error_batch_3d in chunks of whole groups
+    that keep the scratch under gpe.MAX_RECORD_BYTES."""
+    from . import gpe
+    from ._lib import query
+    nx, ny, nz = (len(a) for a in grids)
+    group_bytes = 8 * query("blindno_gpe3d_error_scratch_doubles", per, nx, ny, nz)
+    if group_bytes < 0:
+        raise gpe.BlindnoError(f"the 3D solver refuses a {nx} x {ny} x {nz} grid")
+    fit = int(gpe.MAX_RECORD_BYTES // group_bytes)            # groups per call (the scratch is linear in B)
+    if fit < 1:
+        raise gpe.BlindnoError(
+            f"the scratch of one group of {per} trajectories on the {nx} x {ny} x {nz} grid ({group_bytes} bytes) is "
+            f"above MAX_RECORD_BYTES = {gpe.MAX_RECORD_BYTES}")
+    out = []
+    for s in range(0, len(V), fit * per):
+        e = slice(s, s + fit * per)
+        r = gpe.solve_error_batch_3d(psi0, *grids, dt, t_final, order, np.array(g[e]), np.array(kappa[e]),
+                                     np.array(V[e]), group=per, rec_every=rec_every, device=device)
+        out += [gpe.time_averaged_L2_error_from_sums(r["t"], r["num"][b], r["den"][b]) for b in range(r["num"].shape[0])]
+    return out
+
+
 def compute_time_error_gpe_3d(models: Dict[str, torch.nn.Module], train, test, indices: Iterable[int],
                               outdir: Optional[str] = None, order: int = 2, dt: float = 0.005,
                               t_final: float = 5.0, init_ic: int = 2, batch: int = 2, rec_every: int = 10,
-                              device="cuda") -> Dict[str, np.ndarray]:
+                              device="cuda", record_free: bool = False) -> Dict[str, np.ndarray]:
     """``compute_time_error_gpe_2d`` with the 3D solver and error (``train`` / ``test`` are
     blindno.gpe.generate_training_data_3d dicts; the models map x (B, T, Nx, Ny, Nz) and a
     (Nx, Ny, Nz, 3) grid to V, e.g. NIOFP3D_FNO(..., output_dim=1)): per test index, V predicted by
@@ -242,7 +266,15 @@ def compute_time_error_gpe_3d(models: Dict[str, torch.nn.Module], train, test, i
     gpe.MAX_RECORD_BYTES; the solver is independent of the batch bit for bit, so the chunking does
     not change a digit.  Returns {model: errors in index order}; with ``outdir`` writes
     <outdir>/<model>/sample_<idx>_V_and_err.npy and ErrL2_relative_<model>_Nsamples_<n>.npy as the
-    2D function does (x, y and z in the dict)."""
+    2D function does (x, y and z in the dict).
+
+    With ``record_free=True`` no |psi| record exists: the trajectories go through
+    blindno.gpe.solve_error_batch_3d with group = 1 + len(models), in chunks of whole groups whose
+    scratch (three doubles per cell and trajectory, whatever the number of frames) stays under
+    gpe.MAX_RECORD_BYTES, and the two integrals per frame come back from the device.  The same
+    integrator and the same per-cell terms, summed in another order: the errors agree with the
+    recorded path's to 4 N 2^-53 relative (N cells), and grids whose record the recorded path refuses
+    can be evaluated.  The returned dict and the files are the same."""
     from . import gpe
     sc = evaluate.compute_train_scalers_gpe(train)
     tn = evaluate.normalize_gpe(test, sc)
@@ -269,16 +301,19 @@ def compute_time_error_gpe_3d(models: Dict[str, torch.nn.Module], train, test, i
     psi0 = (gpe.initial_condition(init_ic, x)[:, None, None] * gpe.initial_condition(init_ic, y)[None, :, None] *
             gpe.initial_condition(init_ic, z)[None, None, :])
     per = 1 + len(models)
-    nrec = (int(t_final / dt)) // int(rec_every) + 1
-    traj_bytes = nrec * nx * ny * nz * 8
-    fit = int(gpe.MAX_RECORD_BYTES // traj_bytes)             # trajectories per call
-    if fit < 1:
-        raise gpe.BlindnoError(
-            f"one trajectory's record ({traj_bytes} bytes) is above MAX_RECORD_BYTES = {gpe.MAX_RECORD_BYTES}; "
-            "raise rec_every")
-    chunk = fit // per * per if fit >= per else fit           # whole indices where one fits
     errs = {name: [] for name in models}
     t, rho, base = None, None, 0
+    if record_free:
+        free = _gpe_3d_errors_record_free(psi0, (x, y, z), dt, t_final, order, g, kappa, V, per, rec_every, device)
+    else:
+        nrec = (int(t_final / dt)) // int(rec_every) + 1
+        traj_bytes = nrec * nx * ny * nz * 8
+        fit = int(gpe.MAX_RECORD_BYTES // traj_bytes)             # trajectories per call
+        if fit < 1:
+            raise gpe.BlindnoError(
+                f"one trajectory's record ({traj_bytes} bytes) is above MAX_RECORD_BYTES = {gpe.MAX_RECORD_BYTES}; "
+                "raise rec_every")
+        chunk = fit // per * per if fit >= per else fit           # whole indices where one fits
 
     def traj(n):
         """|psi| record of trajectory n: its chunk is solved when first needed, one chunk resident."""
@@ -293,9 +328,13 @@ def compute_time_error_gpe_3d(models: Dict[str, torch.nn.Module], train, test, i
         return rho[n - base]
 
     for k, i in enumerate(idx):
-        ref = traj(k * per).clone() if chunk % per else traj(k * per)
+        if not record_free:
+            ref = traj(k * per).clone() if chunk % per else traj(k * per)
         for j, name in enumerate(models):
-            e = gpe.time_averaged_L2_error_3d(t, ref, t, traj(k * per + 1 + j), (x, y, z))
+            if record_free:
+                e = free[k * per + 1 + j]
+            else:
+                e = gpe.time_averaged_L2_error_3d(t, ref, t, traj(k * per + 1 + j), (x, y, z))
             errs[name].append(e)
             if outdir is not None:
                 d = os.path.join(outdir, name)

@@ -237,10 +237,19 @@ SIGNATURES_GPE3D_ERR = {
     "blindno_gpe3d_error": "pppp" + "ppp" + "dddd" + "iiii" + "pp" + "iiiii" + "s",
 }
 
+# include/blindno_gpe2d_err.h: the 2D GPE solver without its record, with on-device density-error
+# sums (csrc/gpe2d.hip)
+SIGNATURES_GPE2D_ERR = {
+    "blindno_gpe2d_error_scratch_doubles": "iii",
+    "blindno_gpe2d_error_launches": "iii",
+    "blindno_gpe2d_error": "pppp" + "pp" + "ddd" + "iiii" + "pp" + "iiii" + "s",
+}
+
 # entry points returning int64_t (byte counts) instead of an error code / int count
 RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))} | \
     {n for n in SIGNATURES_GPE3D if n.endswith(("_doubles", "_launches"))} | \
     {n for n in SIGNATURES_GPE3D_ERR if n.endswith(("_doubles", "_launches"))} | \
+    {n for n in SIGNATURES_GPE2D_ERR if n.endswith(("_doubles", "_launches"))} | \
     {n for n in SIGNATURES_FPE if n.endswith("_doubles")} | \
     {n for n in SIGNATURES_FPE_ERR if n.endswith("_doubles")} | \
     {n for n in SIGNATURES_GPE2D if n.endswith(("_doubles", "_launches"))} | \
@@ -271,7 +280,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, sig in {**SIGNATURES, **SIGNATURES_CONV3D, **SIGNATURES_FPE, **SIGNATURES_GPE2D,
                           **SIGNATURES_BAG3D, **SIGNATURES_GPE3D, **SIGNATURES_FPE_ERR,
-                          **SIGNATURES_GPE3D_ERR}.items():
+                          **SIGNATURES_GPE3D_ERR, **SIGNATURES_GPE2D_ERR}.items():
             fn = getattr(lib, name)
             fn.argtypes = [_CT[c] for c in sig]
             fn.restype = ctypes.c_int64 if name in RET64 else ctypes.c_int
@@ -284,7 +293,7 @@ def load():
 def exported_symbols():
     return (list(SIGNATURES) + list(SIGNATURES_CONV3D) + list(SIGNATURES_FPE) + list(SIGNATURES_GPE2D) +
             list(SIGNATURES_BAG3D) + list(SIGNATURES_GPE3D) + list(SIGNATURES_FPE_ERR) +
-            list(SIGNATURES_GPE3D_ERR) + ["blindno_error_string"])
+            list(SIGNATURES_GPE3D_ERR) + list(SIGNATURES_GPE2D_ERR) + ["blindno_error_string"])
 
 
 def stream_ptr(device=None):

@@ -1,6 +1,7 @@
 """Gross-Pitaevskii data generators / density propagators and the density-error metrics on the
 GPU, fp64 like the reference: 1D (libblindno ``blindno_gpe_solve`` / ``blindno_trapz_rows``) and
-2D (``blindno_gpe2d_solve`` / ``blindno_trapz2_frames``, the ``*_2d`` functions) and 3D
+2D (``blindno_gpe2d_solve`` / ``blindno_trapz2_frames``, the ``*_2d`` functions, with the
+record-free ``solve_error_batch_2d`` on ``blindno_gpe2d_error``) and 3D
 (``blindno_gpe3d_solve`` / ``blindno_trapz3_frames``, the ``*_3d`` functions at the end, with the
 record-free ``solve_error_batch_3d`` on ``blindno_gpe3d_error``).
 
@@ -335,6 +336,79 @@ def time_averaged_L2_error_2d(time_ref, rho_ref, time_pred, rho_pred, grid, eps:
     t = d64(time_ref)
     integral = (0.5 * (rel[:-1] + rel[1:]) * (t[1:] - t[:-1])).sum()
     return float(integral / (t[-1] - t[0]))
+
+
+def solve_error_batch_2d(psi0, x, y, dt: float, t_final: float, order: int, g, kappa, V,
+                         group: Optional[int] = None, rec_every: int = 1, device=None):
+    """``solve_batch_2d`` without a record (blindno_gpe2d_error): the same B trajectories, integrated
+    by the same launch sequence, but of every ``rec_every``-th step only the two integrals
+    ``time_averaged_L2_error_2d`` needs come back.  Trajectories come in consecutive groups of
+    ``group`` (default: the whole batch) whose first member is the group's reference.
+
+    psi0, x, y, dt, t_final, order, g, kappa, V: as in ``solve_batch_2d``.  Returns a dict with ``t``
+    (numpy, the recorded times) and the fp64 device tensors ``num`` (B, nrec) =
+    trapz_y trapz_x (|psi_b| - |psi_ref(b)|)^2 and ``den`` (B, nrec) = the same integral of
+    |psi_ref(b)|^2; ``num`` of a reference is exactly 0.  The device holds three doubles per cell and
+    trajectory whatever nrec is (the working field and one |psi| frame), plus two per 1024 cells;
+    ``time_averaged_L2_error_from_sums`` turns a trajectory's two rows into its error.
+
+    Refused before anything is launched (BlindnoError): a batch that is not whole groups, more than
+    MAX_LAUNCHES_2D kernel launches (blindno_gpe2d_error_launches: the solver's plus two per recorded
+    step), scratch above MAX_RECORD_BYTES, and whatever blindno_gpe2d_error refuses."""
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    nx, ny = len(x), len(y)
+    V = np.asarray(V, dtype=np.float64)
+    if V.ndim == 2:
+        V = V[None]
+    if V.ndim != 3 or V.shape[1:] != (nx, ny):
+        raise BlindnoError(f"V has shape {V.shape}; expected (B, {nx}, {ny}) or ({nx}, {ny})")
+    B = V.shape[0]
+    psi0 = np.asarray(psi0, dtype=np.complex128)
+    batched = psi0.ndim == 3
+    if psi0.shape[-2:] != (nx, ny) or psi0.ndim not in (2, 3):
+        raise BlindnoError(f"psi0 has shape {psi0.shape}; expected (B, {nx}, {ny}) or ({nx}, {ny})")
+    if batched and psi0.shape[0] != B:
+        raise BlindnoError("psi0 and V batch sizes differ")
+    g = np.broadcast_to(np.asarray(g, dtype=np.float64), (B,)).copy()
+    kappa = np.broadcast_to(np.asarray(kappa, dtype=np.float64), (B,)).copy()
+    for name, n in (("Nx", nx), ("Ny", ny)):
+        if n & (n - 1) or n < 4 or n > 1024:
+            raise BlindnoError(f"{name} = {n}: the 2D solver needs a power of two in [4, 1024]")
+    if order not in (2, 4):
+        raise BlindnoError(f"order = {order}: the solver has orders 2 and 4")
+    if int(rec_every) < 1:
+        raise BlindnoError(f"rec_every = {rec_every}: must be at least 1")
+    group = B if group is None else int(group)
+    if group < 1 or B % group:
+        raise BlindnoError(f"{B} trajectories are not whole groups of {group}")
+    nt = int(t_final / dt) + 1
+    nsteps = nt - 1
+    nrec = nsteps // int(rec_every) + 1
+    launches = query("blindno_gpe2d_error_launches", nsteps, int(order), int(rec_every))
+    if launches > MAX_LAUNCHES_2D:
+        raise BlindnoError(
+            f"{nsteps} steps of order {order} with {nrec} reduced frames are {launches} kernel launches (limit "
+            f"MAX_LAUNCHES_2D = {MAX_LAUNCHES_2D}); refusing to launch -- raise rec_every or shorten t_final")
+    doubles = query("blindno_gpe2d_error_scratch_doubles", B, nx, ny)
+    if 8 * doubles > MAX_RECORD_BYTES:
+        raise BlindnoError(
+            f"the scratch of {B} trajectories x {nx} x {ny} is {8 * doubles} bytes (limit MAX_RECORD_BYTES = "
+            f"{MAX_RECORD_BYTES}); refusing to launch -- solve fewer groups per call")
+    dev = _dev(device)
+    t_full = np.linspace(0, t_final, nt)
+    # fresh C-ordered copies: the inputs may be read-only or broadcast views
+    p0 = torch.from_numpy(np.array(psi0, order="C").view(np.float64)).to(dev)
+    Vd = torch.from_numpy(np.array(V, order="C")).to(dev)
+    gd = torch.from_numpy(g).to(dev)
+    kd = torch.from_numpy(kappa).to(dev)
+    xd, yd = (torch.from_numpy(np.array(a)).to(dev) for a in (x, y))
+    err = torch.empty(B, nrec, 2, dtype=F64, device=dev)
+    scratch = torch.empty(doubles, dtype=F64, device=dev)
+    call("blindno_gpe2d_error", ptr(p0), ptr(Vd), ptr(gd), ptr(kd), ptr(xd), ptr(yd), float(x[1] - x[0]),
+         float(y[1] - y[0]), float(dt), nsteps, int(order), int(rec_every), group, ptr(err), ptr(scratch), B, nx, ny,
+         int(batched), stream_ptr(dev))
+    return {"t": t_full[::rec_every][:nrec], "num": err[:, :, 0], "den": err[:, :, 1]}
 
 
 # ------------------------------------------------------------------------------------- 3D

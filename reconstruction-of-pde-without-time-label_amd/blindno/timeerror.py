@@ -161,7 +161,7 @@ def compute_time_error_gpe(models: Dict[str, torch.nn.Module], train, test, indi
 def compute_time_error_gpe_2d(models: Dict[str, torch.nn.Module], train, test, indices: Iterable[int],
                               outdir: Optional[str] = None, order: int = 2, dt: float = 0.005,
                               t_final: float = 5.0, init_ic: int = 2, batch: int = 4, rec_every: int = 10,
-                              device="cuda") -> Dict[str, np.ndarray]:
+                              device="cuda", record_free: bool = False) -> Dict[str, np.ndarray]:
     """The 2D counterpart of ``compute_time_error_gpe`` for the 2d_GPE experiment (the
     project's own; ``train`` / ``test`` are blindno.gpe.generate_training_data_2d dicts): per
     test index, V predicted by each model (de-normalised with the train V_max), |psi| propagated
@@ -171,7 +171,15 @@ def compute_time_error_gpe_2d(models: Dict[str, torch.nn.Module], train, test, i
     ``rec_every``-th step (a full 256^2 record of 1001 frames is 0.5 GB per trajectory; the call
     refuses a record above gpe.MAX_RECORD_BYTES).  Returns {model: errors in index order}; with
     ``outdir`` writes <outdir>/<model>/sample_<idx>_V_and_err.npy and
-    ErrL2_relative_<model>_Nsamples_<n>.npy as the 1D function does (x and y in the dict)."""
+    ErrL2_relative_<model>_Nsamples_<n>.npy as the 1D function does (x and y in the dict).
+
+    With ``record_free=True`` no |psi| record exists: the trajectories go through
+    blindno.gpe.solve_error_batch_2d with group = 1 + len(models), in chunks of whole groups whose
+    scratch (three doubles per cell and trajectory, whatever the number of frames) stays under
+    gpe.MAX_RECORD_BYTES, and the two integrals per frame come back from the device.  The same
+    integrator and the same per-cell terms, summed in another order: the errors agree with the
+    recorded path's to 4 N 2^-53 relative (N cells), and test sets whose record the one recorded
+    call refuses can be evaluated.  The returned dict and the files are the same."""
     from . import gpe
     sc = evaluate.compute_train_scalers_gpe(train)
     tn = evaluate.normalize_gpe(test, sc)
@@ -197,15 +205,22 @@ def compute_time_error_gpe_2d(models: Dict[str, torch.nn.Module], train, test, i
             g.append(gi)
             kappa.append(ki)
     psi0 = gpe.initial_condition(init_ic, x)[:, None] * gpe.initial_condition(init_ic, y)[None, :]
-    r = gpe.solve_batch_2d(psi0, x, y, dt, t_final, order, np.array(g), np.array(kappa), np.array(V),
-                           rec_every=rec_every, device=device)
-    t, rho = r["t"], r["abs"]
     per = 1 + len(models)
+    if record_free:
+        free = _gpe_errors_record_free(psi0, (x, y), dt, t_final, order, g, kappa, V, per, rec_every, device)
+    else:
+        r = gpe.solve_batch_2d(psi0, x, y, dt, t_final, order, np.array(g), np.array(kappa), np.array(V),
+                               rec_every=rec_every, device=device)
+        t, rho = r["t"], r["abs"]
     errs = {name: [] for name in models}
     for k, i in enumerate(idx):
-        ref = rho[k * per]
+        if not record_free:
+            ref = rho[k * per]
         for j, name in enumerate(models):
-            e = gpe.time_averaged_L2_error_2d(t, ref, t, rho[k * per + 1 + j], (x, y))
+            if record_free:
+                e = free[k * per + 1 + j]
+            else:
+                e = gpe.time_averaged_L2_error_2d(t, ref, t, rho[k * per + 1 + j], (x, y))
             errs[name].append(e)
             if outdir is not None:
                 d = os.path.join(outdir, name)
@@ -227,26 +242,30 @@ def grid3d(nx: int, ny: int, nz: int, device) -> torch.Tensor:
     return torch.tensor(np.stack(g, axis=3), device=device)
 
 
-def _gpe_3d_errors_record_free(psi0, grids, dt, t_final, order, g, kappa, V, per, rec_every, device) -> List[float]:
-    """time_averaged_L2_error_3d of every trajectory against its group's first (groups of ``per``
-    consecutive trajectories), through blindno.gpe.solve_error_batch_3d in chunks of whole groups
-    that keep the scratch under gpe.MAX_RECORD_BYTES."""
+def _gpe_errors_record_free(psi0, grids, dt, t_final, order, g, kappa, V, per, rec_every, device) -> List[float]:
+    """time_averaged_L2_error_2d / _3d (by the number of ``grids``) of every trajectory against its
+    group's first (groups of ``per`` consecutive trajectories), through
+    blindno.gpe.solve_error_batch_2d / _3d in chunks of whole groups that keep the scratch under
+    gpe.MAX_RECORD_BYTES."""
     from . import gpe
     from ._lib import query
-    nx, ny, nz = (len(a) for a in grids)
-    group_bytes = 8 * query("blindno_gpe3d_error_scratch_doubles", per, nx, ny, nz)
+    dim = f"{len(grids)}d"
+    shape = tuple(len(a) for a in grids)
+    on = " x ".join(str(n) for n in shape)
+    group_bytes = 8 * query(f"blindno_gpe{dim}_error_scratch_doubles", per, *shape)
     if group_bytes < 0:
-        raise gpe.BlindnoError(f"the 3D solver refuses a {nx} x {ny} x {nz} grid")
+        raise gpe.BlindnoError(f"the {dim.upper()} solver refuses a {on} grid")
     fit = int(gpe.MAX_RECORD_BYTES // group_bytes)            # groups per call (the scratch is linear in B)
     if fit < 1:
         raise gpe.BlindnoError(
-            f"the scratch of one group of {per} trajectories on the {nx} x {ny} x {nz} grid ({group_bytes} bytes) is "
+            f"the scratch of one group of {per} trajectories on the {on} grid ({group_bytes} bytes) is "
             f"above MAX_RECORD_BYTES = {gpe.MAX_RECORD_BYTES}")
+    solve = getattr(gpe, f"solve_error_batch_{dim}")
     out = []
     for s in range(0, len(V), fit * per):
         e = slice(s, s + fit * per)
-        r = gpe.solve_error_batch_3d(psi0, *grids, dt, t_final, order, np.array(g[e]), np.array(kappa[e]),
-                                     np.array(V[e]), group=per, rec_every=rec_every, device=device)
+        r = solve(psi0, *grids, dt, t_final, order, np.array(g[e]), np.array(kappa[e]), np.array(V[e]), group=per,
+                  rec_every=rec_every, device=device)
         out += [gpe.time_averaged_L2_error_from_sums(r["t"], r["num"][b], r["den"][b]) for b in range(r["num"].shape[0])]
     return out
 
@@ -304,7 +323,7 @@ def compute_time_error_gpe_3d(models: Dict[str, torch.nn.Module], train, test, i
     errs = {name: [] for name in models}
     t, rho, base = None, None, 0
     if record_free:
-        free = _gpe_3d_errors_record_free(psi0, (x, y, z), dt, t_final, order, g, kappa, V, per, rec_every, device)
+        free = _gpe_errors_record_free(psi0, (x, y, z), dt, t_final, order, g, kappa, V, per, rec_every, device)
     else:
         nrec = (int(t_final / dt)) // int(rec_every) + 1
         traj_bytes = nrec * nx * ny * nz * 8

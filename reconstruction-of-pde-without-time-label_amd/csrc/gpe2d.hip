@@ -1,5 +1,6 @@
 // Grid-resident 2D Gross-Pitaevskii split-step solver and the 2D trapezoid density residual
-// (include/blindno_gpe2d.h).
+// (include/blindno_gpe2d.h), and the solver without its record, with the density-error sums
+// reduced on the device (include/blindno_gpe2d_err.h).
 //
 //   i psi_t = -1/2 (psi_xx + psi_yy) + (V + g |psi|^2 + kappa |psi|^4) psi
 // on a periodic nx x ny grid (row-major, y contiguous, complex128 interleaved), the reference's 1D
@@ -261,6 +262,103 @@ __global__ __launch_bounds__(kTrapzBlock) void trapz2_frames_kernel(
   }
 }
 
+// ---- blindno_gpe2d_error (include/blindno_gpe2d_err.h): the solver with its record reduced away.
+//
+// An error evaluation wants two numbers per trajectory and recorded step, the trapezoid integrals
+// of (|psi| - |psi_ref|)^2 and |psi_ref|^2, not the frames.  The pass kernel above is driven by the
+// same launch sequence as blindno_gpe2d_solve (gpe2d_enqueue below); its |psi| record is pointed at
+// one frame per trajectory in scratch (nrec = 1, record index 0), and after each launch that wrote
+// the frame two small launches reduce it:
+//   stage one  one workgroup of 256 threads per (trajectory, tile of kErrTile consecutive cells):
+//              thread t adds the terms of cells t, t + 256, ... of the tile in ascending order (a
+//              wave's loads are one contiguous 512-B run each), the wave sums by a fixed shuffle
+//              tree (offsets 32, 16 .. 1), lane 0 of the four waves meet in LDS and thread 0 adds
+//              them in wave order -> partial (B, tiles, 2)
+//   stage two  one workgroup per trajectory: thread t adds tiles t, t + 256, ... in ascending
+//              order, then the same tree -> err[b, r, :]
+// The per-cell terms are trapz2_frames_kernel's to the bit (w = wx wy, d = a - b, w (d d) and
+// w (b b); contraction is off for the whole file); only the order of the sum differs.  Every
+// addition has a fixed place, so a second call repeats the bits; a workgroup reads only its own
+// trajectory's frame and its reference's and writes only its own two partials, so the rest of the
+// batch cannot change a group's numbers.  The frame cannot be replaced by reading the field after
+// the column pass: that pass has already applied the next step's first N (has_post2).
+constexpr int kErrTile = BLINDNO_GPE2D_ERR_TILE;
+constexpr int kErrBlock = 256;
+static_assert(kErrTile >= 256 && kErrTile <= 4096 && (kErrTile & (kErrTile - 1)) == 0 &&
+                  kErrTile % kErrBlock == 0,
+              "BLINDNO_GPE2D_ERR_TILE: a power of two in [256, 4096]");
+
+// sum over the workgroup of (a, b), valid in thread 0; `red` is 2 x 4 doubles of LDS
+__device__ __forceinline__ void err_block_sum2(double& a, double& b, double (*red)[kErrBlock / 64]) {
+  for (int off = 32; off > 0; off >>= 1) {
+    a += __shfl_down(a, off, 64);
+    b += __shfl_down(b, off, 64);
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[0][wave] = a;
+    red[1][wave] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a = red[0][0];
+    b = red[1][0];
+    for (int w = 1; w < kErrBlock / 64; ++w) {
+      a += red[0][w];
+      b += red[1][w];
+    }
+  }
+}
+
+// frame (B, N): |psi| of every trajectory at one recorded step; ny is a power of two
+__global__ __launch_bounds__(kErrBlock) void gpe2d_err_tile_kernel(
+    const double* __restrict__ frame, const double* __restrict__ x, const double* __restrict__ y,
+    double* __restrict__ partial, int64_t N, int tiles, int group, int nx, int ny, int lg_ny) {
+  __shared__ double red[2][kErrBlock / 64];
+  const int b = (int)blockIdx.x / tiles;
+  const int tile = (int)blockIdx.x - b * tiles;
+  const double* ap = frame + (int64_t)b * N;
+  const double* bp = frame + (int64_t)(b / group * group) * N;
+  double sa = 0.0, sb = 0.0;
+  for (int k = 0; k < kErrTile / kErrBlock; ++k) {
+    const int64_t e = (int64_t)tile * kErrTile + k * kErrBlock + (int)threadIdx.x;
+    if (e < N) {                                 // N may be smaller than one tile
+      const int iy = (int)(e & (ny - 1));
+      const int ix = (int)(e >> lg_ny);
+      const double wx = 0.5 * ((ix > 0 ? x[ix] - x[ix - 1] : 0.0) + (ix < nx - 1 ? x[ix + 1] - x[ix] : 0.0));
+      const double wy = 0.5 * ((iy > 0 ? y[iy] - y[iy - 1] : 0.0) + (iy < ny - 1 ? y[iy + 1] - y[iy] : 0.0));
+      const double w = wx * wy;
+      const double bv = bp[e], d = ap[e] - bv;
+      sa += w * (d * d);
+      sb += w * (bv * bv);
+    }
+  }
+  err_block_sum2(sa, sb, red);
+  if (threadIdx.x == 0) {
+    partial[2 * (int64_t)blockIdx.x] = sa;
+    partial[2 * (int64_t)blockIdx.x + 1] = sb;
+  }
+}
+
+__global__ __launch_bounds__(kErrBlock) void gpe2d_err_sum_kernel(const double* __restrict__ partial,
+                                                                  double* __restrict__ err, int tiles,
+                                                                  int nrec, int r) {
+  __shared__ double red[2][kErrBlock / 64];
+  const int b = blockIdx.x;
+  const double* pt = partial + 2 * (int64_t)b * tiles;
+  double sa = 0.0, sb = 0.0;
+  for (int t = threadIdx.x; t < tiles; t += kErrBlock) {
+    sa += pt[2 * (int64_t)t];
+    sb += pt[2 * (int64_t)t + 1];
+  }
+  err_block_sum2(sa, sb, red);
+  if (threadIdx.x == 0) {
+    double* e = err + 2 * ((int64_t)b * nrec + r);
+    e[0] = sa;
+    e[1] = sb;
+  }
+}
+
 int ilog2(int v) {
   int l = 0;
   while ((1 << l) < v) ++l;
@@ -315,11 +413,25 @@ BLINDNO_API int64_t blindno_gpe2d_launches(int nsteps, int order) {
   return nsteps == 0 ? 1 : (int64_t)nsteps * (order == 2 ? 2 : 8);
 }
 
-BLINDNO_API int blindno_gpe2d_solve(const double* psi0, const double* V, const double* g,
-                                    const double* kappa, double dx, double dy, double dt, int nsteps,
-                                    int order, int rec_every, void* rec_abs, int rec_abs_f32,
-                                    double* rec_psi, double* psi_out, double* scratch, int B, int nx,
-                                    int ny, int psi0_batched, void* stream) {
+namespace {
+
+// What blindno_gpe2d_error adds to the launch sequence: the frame that takes the record's place and
+// the reduction enqueued after every launch that wrote it.
+struct ErrPlan {
+  const double *x, *y;
+  double* frame;      // (B, N) |psi| of the step being reduced
+  double* partial;    // (B, tiles, 2)
+  double* err;        // (B, nrec, 2)
+  int tiles, group;
+};
+
+// The launch sequence of blindno_gpe2d_solve.  With `E` (blindno_gpe2d_error) the only differences
+// are where the pass kernel records -- E->frame as a one-frame fp64 record, index 0 at every record
+// step -- and the two reduction launches after each launch that recorded.
+int gpe2d_enqueue(const double* psi0, const double* V, const double* g, const double* kappa,
+                  double dx, double dy, double dt, int nsteps, int order, int rec_every, void* rec_abs,
+                  int rec_abs_f32, double* rec_psi, double* psi_out, double* scratch, int B, int nx,
+                  int ny, int psi0_batched, const ErrPlan* E, void* stream) {
   int64_t rb, cb;
   if (!gpe2d_grid(B, nx, ny, &rb, &cb) || nsteps < 0 || rec_every < 1 ||
       (order != 2 && order != 4) || !psi0 || !V || !g || !kappa || !scratch ||
@@ -333,13 +445,21 @@ BLINDNO_API int blindno_gpe2d_solve(const double* psi0, const double* V, const d
   base.V = V;
   base.g = g;
   base.kappa = kappa;
-  base.rec_abs64 = rec_abs_f32 ? nullptr : (double*)rec_abs;
-  base.rec_abs32 = rec_abs_f32 ? (float*)rec_abs : nullptr;
+  base.rec_abs64 = E ? E->frame : rec_abs_f32 ? nullptr : (double*)rec_abs;
+  base.rec_abs32 = !E && rec_abs_f32 ? (float*)rec_abs : nullptr;
   base.rec_psi = rec_psi;
   base.psi_out = psi_out;
   base.nx = nx;
   base.ny = ny;
-  base.nrec = nsteps / rec_every + 1;
+  const int nrec = nsteps / rec_every + 1;
+  base.nrec = E ? 1 : nrec;
+  // record r has just been written to E->frame by the launch before: reduce it into err[:, r, :]
+  auto reduce = [&](int r) -> hipError_t {
+    gpe2d_err_tile_kernel<<<(unsigned)((int64_t)B * E->tiles), kErrBlock, 0, st>>>(
+        E->frame, E->x, E->y, E->partial, N, E->tiles, E->group, nx, ny, ilog2(ny));
+    gpe2d_err_sum_kernel<<<B, kErrBlock, 0, st>>>(E->partial, E->err, E->tiles, nrec, r);
+    return hipGetLastError();
+  };
   base.rec_pre = base.rec_post = -1;
 
   PassArgs row = base, col = base;
@@ -360,7 +480,9 @@ BLINDNO_API int blindno_gpe2d_solve(const double* psi0, const double* V, const d
   if (nsteps == 0) {
     row.do_lin = 0;
     row.write_out = psi_out != nullptr;
-    return (int)launch_pass<false>(row, B, st);
+    hipError_t e = launch_pass<false>(row, B, st);
+    if (e == hipSuccess && E) e = reduce(0);
+    return (int)e;
   }
   // Yoshida coefficients as the reference forms them (2**(1/3) = pow(2, 1/3))
   const double cr = pow(2.0, 1.0 / 3.0);
@@ -381,6 +503,7 @@ BLINDNO_API int blindno_gpe2d_solve(const double* psi0, const double* V, const d
       row.lin_h = col.lin_h = hl[l];
       hipError_t e = launch_pass<false>(row, B, st);
       if (e != hipSuccess) return (int)e;
+      if (E && row.rec_pre >= 0 && (e = reduce(0)) != hipSuccess) return (int)e;
       row.src = scratch;
       row.src_bstride = 2 * N;
       row.rec_pre = -1;
@@ -388,15 +511,66 @@ BLINDNO_API int blindno_gpe2d_solve(const double* psi0, const double* V, const d
       const bool last = l == nl - 1;
       col.has_post1 = 1;
       col.h_post1 = hn[l + 1];
-      col.rec_post = last && n % rec_every == 0 ? n / rec_every : -1;
+      const int rec = last && n % rec_every == 0 ? n / rec_every : -1;
+      col.rec_post = rec >= 0 && E ? 0 : rec;
       col.has_post2 = last && n < nsteps;
       col.h_post2 = hn[0];
       col.write_out = last && n == nsteps && psi_out != nullptr;
       e = launch_pass<true>(col, B, st);
       if (e != hipSuccess) return (int)e;
+      if (E && rec >= 0 && (e = reduce(rec)) != hipSuccess) return (int)e;
     }
   }
   return (int)hipSuccess;
+}
+
+}  // namespace
+
+BLINDNO_API int blindno_gpe2d_solve(const double* psi0, const double* V, const double* g,
+                                    const double* kappa, double dx, double dy, double dt, int nsteps,
+                                    int order, int rec_every, void* rec_abs, int rec_abs_f32,
+                                    double* rec_psi, double* psi_out, double* scratch, int B, int nx,
+                                    int ny, int psi0_batched, void* stream) {
+  return gpe2d_enqueue(psi0, V, g, kappa, dx, dy, dt, nsteps, order, rec_every, rec_abs, rec_abs_f32,
+                       rec_psi, psi_out, scratch, B, nx, ny, psi0_batched, nullptr, stream);
+}
+
+BLINDNO_API int64_t blindno_gpe2d_error_scratch_doubles(int B, int nx, int ny) {
+  int64_t rb, cb;
+  if (!gpe2d_grid(B, nx, ny, &rb, &cb)) return -1;
+  const int64_t N = (int64_t)nx * ny;
+  const int64_t tiles = (N + kErrTile - 1) / kErrTile;
+  return 3 * (int64_t)B * N + 2 * (int64_t)B * tiles;   // field, frame, tile partials
+}
+
+BLINDNO_API int64_t blindno_gpe2d_error_launches(int nsteps, int order, int rec_every) {
+  const int64_t solve = blindno_gpe2d_launches(nsteps, order);
+  if (solve < 0 || rec_every < 1) return -1;
+  return solve + 2 * ((int64_t)(nsteps / rec_every) + 1);
+}
+
+BLINDNO_API int blindno_gpe2d_error(const double* psi0, const double* V, const double* g,
+                                    const double* kappa, const double* x, const double* y, double dx,
+                                    double dy, double dt, int nsteps, int order, int rec_every,
+                                    int group, double* err, double* scratch, int B, int nx, int ny,
+                                    int psi0_batched, void* stream) {
+  int64_t rb, cb;
+  if (!gpe2d_grid(B, nx, ny, &rb, &cb) || group < 1 || B % group != 0 || !x || !y || !err ||
+      !scratch || !aligned16(scratch))
+    return (int)hipErrorInvalidValue;
+  const int64_t N = (int64_t)nx * ny;
+  const int64_t BN = (int64_t)B * N;
+  ErrPlan E;
+  E.x = x;
+  E.y = y;
+  E.frame = scratch + 2 * BN;                  // after the working field
+  E.partial = scratch + 3 * BN;
+  E.err = err;
+  // tiles <= the row pass's workgroups per trajectory, so B * tiles fits the grid as its launch does
+  E.tiles = (int)((N + kErrTile - 1) / kErrTile);
+  E.group = group;
+  return gpe2d_enqueue(psi0, V, g, kappa, dx, dy, dt, nsteps, order, rec_every, nullptr, 0, nullptr,
+                       nullptr, scratch, B, nx, ny, psi0_batched, &E, stream);
 }
 
 BLINDNO_API int blindno_trapz2_frames(const double* a, const double* b, const double* x,

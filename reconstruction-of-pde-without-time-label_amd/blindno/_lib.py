@@ -245,6 +245,18 @@ SIGNATURES_GPE2D_ERR = {
     "blindno_gpe2d_error": "pppp" + "pp" + "ddd" + "iiii" + "pp" + "iiii" + "s",
 }
 
+# include/blindno_nioattn.h: the bag token attention of NIOFP2D_attn in coefficient space
+# (csrc/nioattn.hip)
+SIGNATURES_NIOATTN = {
+    "blindno_nioattn_moments_nblk": "i",
+    "blindno_nioattn_moments_scratch_floats": "ii",
+    "blindno_nioattn_moments": "pppp" + "iii" + "s",
+    "blindno_nioattn_fwd": "ppppppp" + "pppp" + "iiiii" + "s",
+    "blindno_nioattn_bwd_nblk": "i",
+    "blindno_nioattn_bwd_scratch_floats": "iii",
+    "blindno_nioattn_bwd": "pppppppppp" + "pppp" + "iiiiii" + "s",
+}
+
 # entry points returning int64_t (byte counts) instead of an error code / int count
 RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))} | \
     {n for n in SIGNATURES_GPE3D if n.endswith(("_doubles", "_launches"))} | \
@@ -253,7 +265,8 @@ RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))} | \
     {n for n in SIGNATURES_FPE if n.endswith("_doubles")} | \
     {n for n in SIGNATURES_FPE_ERR if n.endswith("_doubles")} | \
     {n for n in SIGNATURES_GPE2D if n.endswith(("_doubles", "_launches"))} | \
-    {n for n in SIGNATURES_BAG3D if n.endswith("_floats")}
+    {n for n in SIGNATURES_BAG3D if n.endswith("_floats")} | \
+    {n for n in SIGNATURES_NIOATTN if n.endswith("_floats")}
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_int64, "f": ctypes.c_float,
        "d": ctypes.c_double, "s": ctypes.c_void_p}
@@ -280,7 +293,8 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         for name, sig in {**SIGNATURES, **SIGNATURES_CONV3D, **SIGNATURES_FPE, **SIGNATURES_GPE2D,
                           **SIGNATURES_BAG3D, **SIGNATURES_GPE3D, **SIGNATURES_FPE_ERR,
-                          **SIGNATURES_GPE3D_ERR, **SIGNATURES_GPE2D_ERR}.items():
+                          **SIGNATURES_GPE3D_ERR, **SIGNATURES_GPE2D_ERR,
+                          **SIGNATURES_NIOATTN}.items():
             fn = getattr(lib, name)
             fn.argtypes = [_CT[c] for c in sig]
             fn.restype = ctypes.c_int64 if name in RET64 else ctypes.c_int
@@ -293,7 +307,8 @@ def load():
 def exported_symbols():
     return (list(SIGNATURES) + list(SIGNATURES_CONV3D) + list(SIGNATURES_FPE) + list(SIGNATURES_GPE2D) +
             list(SIGNATURES_BAG3D) + list(SIGNATURES_GPE3D) + list(SIGNATURES_FPE_ERR) +
-            list(SIGNATURES_GPE3D_ERR) + list(SIGNATURES_GPE2D_ERR) + ["blindno_error_string"])
+            list(SIGNATURES_GPE3D_ERR) + list(SIGNATURES_GPE2D_ERR) + list(SIGNATURES_NIOATTN) +
+            ["blindno_error_string"])
 
 
 def stream_ptr(device=None):

@@ -9,6 +9,8 @@ encoder kernels and the 1D GPE head layout:
                             (2d_FPE/NIOModules.py:14-83,508-581; 2d_FPE/Baselines.py:200)
   2d_Non_conservative_FPE   heads fno_Fx, fno_Fy; Encoder2D (3,2)
                             (2d_Non_conservative_FPE/NIOModules.py:13-82,503-577; Baselines.py:200)
+  both 2D experiments       NIOFP2D_attn (2d_FPE/NIOModules.py:410-504) with the same heads and
+                            Encoder2D kernels as NIOFP2D (blindno.nio.NIOFP2D_attn)
   1d_FPE                    NIOFP / NIOFP_FNO heads fno_drift, fno_diffusion; Encoder (5,4,15)
                             (1d_FPE/NIOModules.py:15-155; 1d_FPE/Baselines.py:254-287)
   1d_GPE                    NIOFP_schrodinger / NIOFP_FNO head fno_V; Encoder (5,7,4) + conv4
@@ -90,6 +92,22 @@ class _NIOFP2D_FNO_attn_nc(_nio.NIOFP2D_FNO_attn):
                          width, modes, output_dim, nx, ny, heads=("fno_Fx", "fno_Fy"))
 
 
+class _NIOFP2D_attn_2d(_nio.NIOFP2D_attn):
+    def __init__(self, input_dimensions_trunk, n_hidden_layers, neurons, n_basis, fno_layers,
+                 width, modes, output_dim):
+        super().__init__(input_dimensions_trunk, n_hidden_layers, neurons, n_basis, fno_layers,
+                         width, modes, output_dim, heads=("fno_drift", "fno_diffusion"),
+                         branch_last_kernel=(2, 1))
+
+
+class _NIOFP2D_attn_nc(_nio.NIOFP2D_attn):
+    def __init__(self, input_dimensions_trunk, n_hidden_layers, neurons, n_basis, fno_layers,
+                 width, modes, output_dim):
+        super().__init__(input_dimensions_trunk, n_hidden_layers, neurons, n_basis, fno_layers,
+                         width, modes, output_dim, heads=("fno_Fx", "fno_Fy"),
+                         branch_last_kernel=(3, 2))
+
+
 # ------------------------------------------------------------------------------- 1D
 class _NIOFP_FNO_1d(_nio.NIOFP_FNO):
     def __init__(self, fno_layers, width, modes, output_dim, device):
@@ -126,20 +144,21 @@ def _oos(where, *names):
     return {n: _out_of_scope(n, where) for n in names}
 
 
-_2D_OOS = ("NIOFP2D_Trans", "NIOFP2D_Trans_attn", "NIOFP2D_attn",
-           "NIOFP_ode", "PermInvUNet")
+_2D_OOS = ("NIOFP2D_Trans", "NIOFP2D_Trans_attn", "NIOFP_ode", "PermInvUNet")
 
 EXPERIMENTS = {
     "2d_FPE": dict(
         NIOModules=dict(NIOFP2D=_NIOFP2D_2d, NIOFP2D_FNO=_NIOFP2D_FNO_2d, NIOFP=_NIOFP_1d,
-                        NIOFP2D_FNO_attn=_NIOFP2D_FNO_attn_2d, NIOFP3D=_nio.NIOFP3D,
+                        NIOFP2D_FNO_attn=_NIOFP2D_FNO_attn_2d, NIOFP2D_attn=_NIOFP2D_attn_2d,
+                        NIOFP3D=_nio.NIOFP3D,
                         PermInvUNet_attn=_unet.PermInvUNet_attn, ConvNeXtBlock=_unet.ConvNeXtBlock,
                         TemporalSelfAttention=_unet.TemporalSelfAttention,
                         draw_bag=_nio.draw_bag, **_oos("2d_FPE/NIOModules.py", *_2D_OOS)),
     ),
     "2d_Non_conservative_FPE": dict(
         NIOModules=dict(NIOFP2D=_NIOFP2D_nc, NIOFP2D_FNO=_NIOFP2D_FNO_nc, NIOFP=_NIOFP_1d,
-                        NIOFP2D_FNO_attn=_NIOFP2D_FNO_attn_nc, NIOFP3D=_nio.NIOFP3D,
+                        NIOFP2D_FNO_attn=_NIOFP2D_FNO_attn_nc, NIOFP2D_attn=_NIOFP2D_attn_nc,
+                        NIOFP3D=_nio.NIOFP3D,
                         PermInvUNet_attn=_unet.PermInvUNet_attn_NC,
                         TemporalSelfAttention=_unet.TemporalSelfAttention,
                         draw_bag=_nio.draw_bag,

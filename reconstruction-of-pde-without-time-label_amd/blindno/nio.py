@@ -1,4 +1,4 @@
-"""Snapshot-bag (time-label-free) models: NIOFP2D_FNO, NIOFP_FNO, NIOFP2D, NIOFP,
+"""Snapshot-bag (time-label-free) models: NIOFP2D_FNO, NIOFP_FNO, NIOFP2D, NIOFP2D_attn, NIOFP,
 NIOFP_schrodinger, NIOFP3D -- drop-in for the reference's NIOModules -- and NIOFP3D_FNO, the
 project's own 3D FNO-NIO (the reference has no such class).
 
@@ -350,6 +350,49 @@ class NIOFP2D(nn.Module):
         ubar = ops.DeepONetBagFn.apply(w, basis, self.deeponet.b0)
         h = _bag_mean_2d(self, ubar.view(B, 1, nx * ny), grid, B, 1, nx, ny)
         return _run_heads(self, h)          # the two FNO heads as one grouped launch chain
+
+
+class NIOFP2D_attn(nn.Module):
+    """NIO branch/trunk with the bag token attention, 2d_FPE/NIOModules.py:410-504 (NC copy with
+    heads fno_Fx/fno_Fy: 2d_Non_conservative_FPE/NIOModules.py:406-).
+
+    The DeepONet branch and trunk of NIOFP2D, then the attention of NIOFP2D_FNO_attn over the
+    tokens [gx, gy, u_1..u_L] with u_l = (w_l . basis + b0) / sqrt(n_basis), fused with fc0 =
+    Linear(1, width) (``.data``), then the two FNO heads.  ops.NIOAttnFn runs the attention on the
+    tokens' coefficients (they have rank <= n_basis + 3), so the (B, L, nx ny) field is never
+    formed.  Registration order (trunk, branch, deeponet, fc0, heads) follows the reference.
+
+    The train-mode draw is WITH replacement (:449-450, unlike NIOFP2D_FNO_attn) and duplicates stay
+    duplicate tokens: the branch's BatchNorm statistics and the softmax normaliser count them."""
+
+    def __init__(self, input_dimensions_trunk, n_hidden_layers, neurons, n_basis, fno_layers,
+                 width, modes, output_dim, heads: Sequence[str] = ("fno_drift", "fno_diffusion"),
+                 branch_last_kernel=(2, 1)):
+        super().__init__()
+        output_dimensions = n_basis
+        self.trunk = FFN(input_dimensions_trunk, output_dimensions, n_hidden_layers, neurons,
+                         "leaky_relu", 0.0)
+        self.fno_layers = fno_layers
+        self.branch = Encoder2D(output_dimensions, last_kernel=branch_last_kernel)
+        self.deeponet = DeepOnetNoBiasOrg(self.branch, self.trunk)
+        self.fc0 = nn.Linear(1, width)
+        self._heads = tuple(heads)
+        for name in self._heads:
+            setattr(self, name, FNO2d(modes=modes, width=width, n_layers=self.fno_layers,
+                                      input_dim=width, output_dim=1))
+
+    def forward(self, x, grid, bag_idx=None):
+        """x (B, T, nx, ny), grid (nx, ny, 2) -> (B, nx, ny, 2).  ``bag_idx`` overrides the
+        train-mode draw (a host index list or a device int tensor); eval mode uses all T."""
+        ops.require_device(x, grid)
+        x, L, _ = _select(self, x, bag_idx)        # no dedup: duplicates are tokens of their own
+        B, _, nx, ny = x.shape
+        w = self.deeponet.branch(x.unsqueeze(2))                   # (B, L, n_basis)
+        g = grid.reshape(-1, 2)
+        basis = self.deeponet.trunk(g)                             # (nx ny, n_basis)
+        h = ops.NIOAttnFn.apply(w, basis, self.deeponet.b0, g, self.fc0.weight.data,
+                                self.fc0.bias.data)
+        return _run_heads(self, h.view(B, nx, ny, -1))
 
 
 class NIOFP3D(nn.Module):

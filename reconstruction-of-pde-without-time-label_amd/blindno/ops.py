@@ -2308,6 +2308,70 @@ class BagAttnFn(torch.autograd.Function):
         return (du if ctx.needs_input_grad[0] else None), ggrid, None, None
 
 
+class NIOAttnFn(torch.autograd.Function):
+    """DeepONet combiner + bag token attention + fixed-weight fusion of NIOFP2D_attn
+    (2d_FPE/NIOModules.py:459-495) in coefficient space (csrc/nioattn.hip, include/blindno_nioattn.h):
+    w (B, L, P) branch coefficients, basis (S, P) trunk output, b0 scalar, grid (S, 2) ->
+    (B, S, width).  The tokens [gx, gy, (w_l . basis + b0) / sqrt(P)] have rank <= P + 3, so the
+    attention runs on their coefficients and the (B, L, S) field is never formed.
+    ``fc0_weight`` / ``fc0_bias`` are ``fc0.weight.data`` / ``.bias.data`` (fc0 = Linear(1, width),
+    never trained).  Gradients for w, basis and b0; none for the grid."""
+
+    @staticmethod
+    def forward(ctx, w, basis, b0, grid, fc0_weight, fc0_bias):
+        require_device(w, basis, b0, grid, fc0_weight, fc0_bias)
+        if ctx.needs_input_grad[3] or grid.requires_grad:
+            raise BlindnoError("NIOAttnFn produces no grid gradient (grid.requires_grad is set)")
+        ctx.b0_shape = tuple(b0.shape)
+        w, basis, b0, grid = _c(w), _c(basis), _c(b0.reshape(1)), _c(grid)
+        fw, fb = _c(fc0_weight.detach()).view(-1), _c(fc0_bias.detach())
+        B, L, P = w.shape
+        S = basis.shape[0]
+        T, Q, width = L + 2, P + 3, fw.numel()
+        if basis.shape[1] != P:
+            raise BlindnoError(f"nioattn: branch {tuple(w.shape)} / trunk {tuple(basis.shape)} mismatch")
+        if P > 64:
+            raise BlindnoError(f"nioattn: at most 64 basis functions (n_basis = 25 in every reference "
+                               f"script), got {P}")
+        if T > 256:
+            raise BlindnoError(f"bag attention supports at most 256 tokens (L + 2), got {T}")
+        if tuple(grid.shape) != (S, 2) or fb.numel() != width:
+            raise BlindnoError(f"nioattn: grid {tuple(grid.shape)} / fc0 {tuple(fw.shape)} do not "
+                               f"match S={S}")
+        nblk = query("blindno_nioattn_moments_nblk", S)
+        partial = _empty(query("blindno_nioattn_moments_scratch_floats", S, P), like=w)
+        M = _empty(Q, Q, like=w)
+        call("blindno_nioattn_moments", ptr(grid), ptr(basis), ptr(partial), ptr(M), nblk, S, P,
+             stream_ptr())
+        A = _empty(B, T, T, like=w)
+        cs = _empty(B, T, like=w)
+        v = _empty(B, Q, like=w)
+        y = _empty(B, S, width, like=w)
+        call("blindno_nioattn_fwd", ptr(w), ptr(b0), ptr(basis), ptr(grid), ptr(M), ptr(fw), ptr(fb),
+             ptr(A), ptr(cs), ptr(v), ptr(y), B, L, S, P, width, stream_ptr())
+        ctx.save_for_backward(w, basis, b0, grid, fw, M, A, cs, v)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        w, basis, b0, grid, fw, M, A, cs, v = ctx.saved_tensors
+        B, L, P = w.shape
+        S = basis.shape[0]
+        gy = _c(gy)
+        nblk = query("blindno_nioattn_bwd_nblk", S)
+        scratch = _empty(query("blindno_nioattn_bwd_scratch_floats", B, S, P), like=gy)
+        dw = _empty(B, L, P, like=gy)
+        dbasis = _empty(S, P, like=gy)
+        db0 = _empty(1, like=gy)
+        call("blindno_nioattn_bwd", ptr(gy), ptr(w), ptr(b0), ptr(basis), ptr(grid), ptr(M), ptr(fw),
+             ptr(A), ptr(cs), ptr(v), ptr(scratch), ptr(dw), ptr(dbasis), ptr(db0), nblk, B, L, S, P,
+             fw.numel(), stream_ptr())
+        # one launch sequence forms all three; hand back only what was asked for
+        need = ctx.needs_input_grad
+        return (dw if need[0] else None, dbasis if need[1] else None,
+                db0.reshape(ctx.b0_shape) if need[2] else None, None, None, None)
+
+
 # ---------------------------------------------------------------------------- loss
 
 

@@ -1,0 +1,220 @@
+"""NIOFP2D_attn (2d_FPE/NIOModules.py:410-504) without a GPU: the two float64 restatements of its
+coefficient-space attention against each other, the model-level restatement against the reference's
+golden, the state_dict layout, the train-mode draw, both drop-in shims and the C ABI binding.
+
+The GPU tests (tests/test_gpu_nioattn.py) compare the kernels of csrc/nioattn.hip against
+nio2d_attn_ref.attn_math; here attn_math itself is tied to the reference's own composition
+(attn_direct: tokens materialised, oracle.fno_ref.bag_attention, float64 autograd) in the three
+logit regimes of the GPU tests, to the 1e-11 that tests/test_gpu_bagagg.py holds its two float64
+statements to.
+"""
+import json
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import nio2d_attn_ref
+from conftest import GOLDEN, ROOT, load_golden, rel_l2
+from recipe import make_array, make_state
+
+DROPIN = os.path.join(ROOT, "dropin")
+CTOR = (2, 3, 100, 25, 3, 12, 32, 2)
+FP64_AGREE = 1e-11
+
+# (B, L, S, P, width) and the regimes: the cases of tests/test_gpu_nioattn.py
+from nioattn_cases import REGIMES, SHAPES, make_case  # noqa: E402
+
+
+def _rel(a, b):
+    a, b = a.double(), b.double()
+    return float(torch.linalg.vector_norm(a - b) / torch.linalg.vector_norm(b).clamp_min(1e-300))
+
+
+@pytest.mark.parametrize("regime", REGIMES)
+@pytest.mark.parametrize("B,L,S,P,width", SHAPES)
+def test_two_fp64_statements_agree(B, L, S, P, width, regime):
+    inputs, ref = make_case(B, L, S, P, width, regime)        # asserts the regime
+    direct = nio2d_attn_ref.attn_direct(*inputs)
+    for k in ("y", "dw", "dbasis", "db0"):
+        e = _rel(ref[k], direct[k])
+        assert e <= FP64_AGREE, (k, e)
+    # M is symmetric, A's rows sum to one, cs sums to T
+    assert torch.equal(ref["M"], ref["M"].t()) or _rel(ref["M"], ref["M"].t()) <= 1e-15
+    assert float((ref["A"].sum(-1) - 1).abs().max()) <= 1e-12
+    assert float((ref["cs"].sum(-1) - (L + 2)).abs().max()) <= 1e-10
+
+
+def _golden_params(g, dtype=torch.float64):
+    shapes = [(k, tuple(s)) for k, s in json.loads(str(g["layout_json"]))]
+    st = make_state(shapes, seed=int(g["recipe_seed"]))
+    return st, {k: torch.from_numpy(v).to(dtype).requires_grad_(v.dtype.kind == "f") for k, v in st.items()}
+
+
+def golden_x(g):
+    return float(g["amp"]) * make_array(tuple(int(n) for n in g["x_shape"]), int(g["recipe_seed"]), "nio2d_attn.x")
+
+
+def test_golden_model_restatement():
+    """nio2d_attn_ref.niofp2d_attn on the nio2d_attn_train golden (80^2, one bag, 51 recorded draws
+    with replacement from 52 snapshots), at the bars of test_oracle_golden.py::test_niofp2d_nio_branch_trunk."""
+    g = load_golden("nio2d_attn_train")
+    idx = g["idx"].tolist()
+    assert tuple(g["x_shape"]) == (1, 52, 80, 80) and len(idx) == int(g["L"]) == 51
+    assert len(set(idx)) < len(idx)                       # at least one duplicate index
+    assert os.path.getsize(os.path.join(GOLDEN, "nio2d_attn_train.npz")) < \
+        os.path.getsize(os.path.join(GOLDEN, "nio2d_nc_train.npz"))
+    _, p = _golden_params(g)
+    x = torch.from_numpy(golden_x(g)).double()
+    grid = torch.from_numpy(g["in.grid"]).double()
+    rec = {}
+    y = nio2d_attn_ref.niofp2d_attn(p, x, grid, idx=idx, heads=("fno_Fx", "fno_Fy"), record=rec)
+    assert rel_l2(y.detach().numpy(), g["out"]) <= 1e-4
+    (y * torch.from_numpy(g["cot"]).double()).sum().backward()
+    gmax = max(float(v) for k, v in g.items() if k.startswith("gnorm."))
+    n = 0
+    for k, v in g.items():
+        if k.startswith("g."):
+            assert p[k[2:]].grad is not None, k
+            assert rel_l2(p[k[2:]].grad.numpy(), v) <= 1e-3, k
+            n += 1
+        if k.startswith("gnorm."):
+            got = float(p[k[6:]].grad.norm())
+            assert abs(got - float(v)) <= 1e-3 * abs(float(v)) + 1e-5 * gmax, k
+    assert n > 30 and any(k.startswith("g.trunk.") for k in g) and "g.deeponet.b0" in g
+    assert not any(k.startswith(("g.fc0.", "gnorm.fc0.")) for k in g)     # fc0 is read through .data
+    # anti-hiding: the attention matters in this fixture.  The recorded mean row maximum of A is
+    # the restatement's, and a uniform A moves the float64 output (and the fused field the heads
+    # read) by at least 10 x the forward bar
+    rowmax = float(rec["A"].max(-1).values.mean())
+    assert abs(rowmax - float(g["A_rowmax_mean"])) <= 1e-4
+    move = rel_l2(rec["h_uniform"].numpy(), rec["h"].numpy())
+    move_out = rel_l2(rec["y_uniform"].numpy(), y.detach().numpy())
+    print(f"uniform attention moves the fused field by {move:.2e}, the output by {move_out:.2e}")
+    assert move >= 10 * 1e-4, move
+    assert move_out >= 10 * 1e-4, move_out
+
+
+def test_state_dict_layout_matches_reference():
+    import blindno
+    lay = json.load(open(os.path.join(GOLDEN, "layouts_nio2d_attn.json")))
+    for key, kw in (("2d_FPE", dict(heads=("fno_drift", "fno_diffusion"), branch_last_kernel=(2, 1))),
+                    ("2d_NC", dict(heads=("fno_Fx", "fno_Fy"), branch_last_kernel=(3, 2)))):
+        m = blindno.NIOFP2D_attn(*CTOR, **kw)
+        got = [[k, list(v.shape), str(v.dtype).replace("torch.", "")] for k, v in m.state_dict().items()]
+        assert got == lay[f"{key}.NIOFP2D_attn(2,3,100,25,3,12,32,2)"]
+        assert tuple(m.fc0.weight.shape) == (12, 1)
+
+
+def test_train_mode_draw_is_the_references(monkeypatch):
+    """randint(50, T) then choice(T, L) WITH replacement from numpy's global RNG, once per forward."""
+    import blindno
+    from blindno import nio, ops
+    seen = {}
+
+    def fake_apply(w, basis, b0, grid, fw, fb):
+        seen["L"] = w.shape[1]
+        return torch.zeros(w.shape[0], basis.shape[0], fw.numel())
+
+    class Branch(torch.nn.Module):                          # records which snapshots it was given
+        def forward(self, xb):
+            picked.append(xb[0, :, 0, 0, 0].clone())
+            return torch.zeros(xb.shape[0], xb.shape[1], 3)
+
+    class Trunk(torch.nn.Module):
+        def forward(self, g):
+            return torch.zeros(g.shape[0], 3)
+
+    class Don(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.branch, self.trunk, self.b0 = Branch(), Trunk(), torch.zeros(())
+
+    picked = []
+    m = blindno.NIOFP2D_attn(2, 2, 8, 3, 1, 2, 2, 2)
+    m.deeponet = Don()
+    m.train()
+    monkeypatch.setattr(ops, "require_device", lambda *a: None)
+    monkeypatch.setattr(ops.NIOAttnFn, "apply", staticmethod(fake_apply))
+    monkeypatch.setattr(nio, "_run_heads", lambda mod, h: h)
+    T = 60
+    x = torch.arange(T, dtype=torch.float32).view(1, T, 1, 1).expand(1, T, 4, 4).contiguous()
+    grid = torch.zeros(4, 4, 2)
+    np.random.seed(5)
+    L = np.random.randint(50, T)
+    idx = np.random.choice(T, L)
+    after = np.random.randint(1 << 30)
+    np.random.seed(5)
+    m(x, grid)
+    assert np.random.randint(1 << 30) == after            # the same two draws, nothing more
+    assert seen["L"] == L and picked[0].tolist() == [float(i) for i in idx]
+    assert len(set(idx.tolist())) < L                     # duplicates stay duplicate tokens
+    m.eval()
+    m(x, grid)
+    assert seen["L"] == T
+
+
+def test_grid_gradient_is_refused(monkeypatch):
+    from blindno import BlindnoError, ops
+    monkeypatch.setattr(ops, "require_device", lambda *a: None)
+    g = torch.zeros(4, 2, requires_grad=True)
+    with pytest.raises(BlindnoError, match="grid gradient"):
+        ops.NIOAttnFn.apply(torch.zeros(1, 2, 3), torch.zeros(4, 3), torch.zeros(()), g,
+                            torch.zeros(2, 1), torch.zeros(2))
+
+
+def _run(code, exp):
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
+    return subprocess.run([sys.executable, "-c",
+                           f"import sys; sys.path.insert(0, {os.path.join(DROPIN, exp)!r})\n" + code],
+                          capture_output=True, text=True, env=env, timeout=240)
+
+
+@pytest.mark.parametrize("exp,heads", [("2d_FPE", ["fno_drift", "fno_diffusion"]),
+                                       ("2d_Non_conservative_FPE", ["fno_Fx", "fno_Fy"])])
+def test_dropin_shims_serve_the_class(exp, heads):
+    r = _run("from NIOModules import NIOFP2D_attn\n"
+             "m = NIOFP2D_attn(2,3,100,25,3,12,32,2)\n"
+             "print(type(m).__mro__[1].__name__, sorted(n for n, _ in m.named_children()),"
+             " list(m.branch.convblock7_3.layers[0].kernel_size))\n", exp)
+    assert r.returncode == 0, r.stderr
+    kernel = [2, 1] if exp == "2d_FPE" else [3, 2]
+    assert r.stdout.strip() == f"NIOFP2D_attn {sorted(['branch', 'deeponet', 'fc0', 'trunk'] + heads)} {kernel}", \
+        (r.stdout, r.stderr)
+
+
+def test_nioattn_symbols_declared_and_bound():
+    """include/blindno_nioattn.h (included by blindno.h) <=> _lib.SIGNATURES_NIOATTN <=> the library."""
+    import blindno
+    from blindno import _lib
+    assert '#include "blindno_nioattn.h"' in open(os.path.join(ROOT, "include", "blindno.h")).read()
+    hdr = open(os.path.join(ROOT, "include", "blindno_nioattn.h")).read()
+    decl = sorted(set(re.findall(r"^(?:int|int64_t|const char\*)\s+(blindno_\w+)\(", hdr, re.M)))
+    assert decl == sorted(_lib.SIGNATURES_NIOATTN) and len(decl) == 7
+    assert {"blindno_nioattn_moments", "blindno_nioattn_fwd", "blindno_nioattn_bwd"} <= set(decl)
+    assert not set(_lib.SIGNATURES_NIOATTN) & set(_lib.SIGNATURES)
+    lib = blindno.load_library()
+    for s in decl:
+        assert hasattr(lib, s) and s in _lib.exported_symbols(), s
+        m = re.search(r"\b(?:int|int64_t)\s+" + s + r"\s*\(([^;]*)\)\s*;", hdr)
+        nargs = len([a for a in m.group(1).split(",") if a.strip()])
+        assert nargs == len(_lib.SIGNATURES_NIOATTN[s]) == len(getattr(lib, s).argtypes), (s, nargs)
+    q = _lib.query
+    assert q("blindno_nioattn_moments_nblk", 16384) == 128 and q("blindno_nioattn_moments_nblk", 513) == 5
+    assert q("blindno_nioattn_moments_scratch_floats", 16384, 25) == 128 * 28 * 28
+    assert q("blindno_nioattn_bwd_nblk", 16384) == 128 and q("blindno_nioattn_bwd_nblk", 129) == 2
+    assert q("blindno_nioattn_bwd_scratch_floats", 4, 16384, 25) == \
+        4 * 16384 + 128 * 4 * 28 + 4 * 28 * 28 + 28 * 28 + 4
+    assert q("blindno_nioattn_bwd_scratch_floats", 1 << 20, 1 << 14, 64) > 2 ** 32
+    for bad in [(0, 25), (64, 0), (64, 65), (-1, 25)]:
+        assert q("blindno_nioattn_moments_scratch_floats", *bad) == -1, bad
+    assert q("blindno_nioattn_bwd_scratch_floats", 0, 64, 25) == -1
+    assert q("blindno_nioattn_moments_nblk", 0) == -1 and q("blindno_nioattn_bwd_nblk", 0) == -1
+    sys.path.insert(0, os.path.join(ROOT, "reconstruction-of-pde-without-time-label_amd"))
+    import build as _b
+    import glob
+    assert "nioattn.hip" in [os.path.basename(p) for p in glob.glob(os.path.join(_b.CSRC, "*.hip"))]

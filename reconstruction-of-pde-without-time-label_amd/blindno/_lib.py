@@ -197,7 +197,7 @@ SIGNATURES_FPE = {
 }
 
 # include/blindno_gpe2d.h: the grid-resident 2D GPE solver and the 2D trapezoid residual
-# (csrc/gpe2d.hip)
+# (csrc/gpe_nd.hip)
 SIGNATURES_GPE2D = {
     "blindno_gpe2d_scratch_doubles": "iii",
     "blindno_gpe2d_launches": "ii",
@@ -214,7 +214,7 @@ SIGNATURES_BAG3D = {
 }
 
 # include/blindno_gpe3d.h: the grid-resident 3D GPE solver and the 3D trapezoid residual
-# (csrc/gpe3d.hip)
+# (csrc/gpe_nd.hip)
 SIGNATURES_GPE3D = {
     "blindno_gpe3d_scratch_doubles": "iiii",
     "blindno_gpe3d_launches": "ii",
@@ -230,7 +230,7 @@ SIGNATURES_FPE_ERR = {
 }
 
 # include/blindno_gpe3d_err.h: the 3D GPE solver without its record, with on-device density-error
-# sums (csrc/gpe3d.hip)
+# sums (csrc/gpe_nd.hip)
 SIGNATURES_GPE3D_ERR = {
     "blindno_gpe3d_error_scratch_doubles": "iiii",
     "blindno_gpe3d_error_launches": "iii",
@@ -238,7 +238,7 @@ SIGNATURES_GPE3D_ERR = {
 }
 
 # include/blindno_gpe2d_err.h: the 2D GPE solver without its record, with on-device density-error
-# sums (csrc/gpe2d.hip)
+# sums (csrc/gpe_nd.hip)
 SIGNATURES_GPE2D_ERR = {
     "blindno_gpe2d_error_scratch_doubles": "iii",
     "blindno_gpe2d_error_launches": "iii",

@@ -171,19 +171,180 @@ def time_averaged_L2_error(time_ref, rho_ref, time_pred, rho_pred, grid, eps: fl
     return float(integral / (t[-1] - t[0]))
 
 
-# ------------------------------------------------------------------------------------- 2D
+# ------------------------------------------------------------------------------ 2D and 3D
 # The reference lists a 2D GPE experiment and ships no code for it; what follows is the project's
-# own: the 1D scheme above carried to two dimensions (csrc/gpe2d.hip, grid-resident: the field
-# lives in global memory and every kinetic step is a row launch plus a column launch).
+# own: the 1D scheme above carried to two and three dimensions (csrc/gpe_nd.hip, grid-resident:
+# the field lives in global memory and every kinetic step is one launch per axis).  The ``_*_nd``
+# functions are the bodies; the public ``*_2d`` / ``*_3d`` functions pass them their grids and
+# their launch limit, and everything else follows from the number of grids.
 
 # The launches one solve_batch_2d call may enqueue (2 per Strang step, 8 per Yoshida step).
 # Largest power of two whose worst case stays under 120 s at the time per launch measured by
 # tools/bench_gpe2d.py at 256^2, B = 16 (profiles/gpe2d_bench.json: 31.16 us per launch;
 # 120 s / 31.16 us = 3.85 M, 2^21 launches take 65.4 s and 2^22 would take 130.7 s).
 MAX_LAUNCHES_2D = 1 << 21
+# The launches one solve_batch_3d call may enqueue (3 per Strang step, 12 per Yoshida step).  The
+# rule of MAX_LAUNCHES_2D: the largest power of two whose worst case stays under 120 s at the time
+# per launch measured by tools/bench_gpe3d.py at its headline shape, 64^3 with B = 16
+# (profiles/gpe3d_bench.json: 77.39 us per launch; 120 s / 77.39 us = 1.55 M, 2^20 launches take
+# 81.1 s and 2^21 would take 162.3 s).
+MAX_LAUNCHES_3D = 1 << 20
 # The bytes of record (|psi| and psi together) one call may allocate: 8 GiB.
 MAX_RECORD_BYTES = 8 << 30
 
+
+def _problem_nd(psi0, grids, g, kappa, V, order, rec_every):
+    """The host-side checks that the solve and error functions share, in their order.  Returns
+    (grids, shape, psi0, batched, g, kappa, V) as fp64 / complex128 numpy, V with its batch axis."""
+    grids = [np.asarray(a, dtype=np.float64) for a in grids]
+    dim = len(grids)
+    shape = tuple(len(a) for a in grids)
+    dims = ", ".join(str(n) for n in shape)
+    V = np.asarray(V, dtype=np.float64)
+    if V.ndim == dim:
+        V = V[None]
+    if V.ndim != dim + 1 or V.shape[1:] != shape:
+        raise BlindnoError(f"V has shape {V.shape}; expected (B, {dims}) or ({dims})")
+    B = V.shape[0]
+    psi0 = np.asarray(psi0, dtype=np.complex128)
+    batched = psi0.ndim == dim + 1
+    if psi0.shape[-dim:] != shape or psi0.ndim not in (dim, dim + 1):
+        raise BlindnoError(f"psi0 has shape {psi0.shape}; expected (B, {dims}) or ({dims})")
+    if batched and psi0.shape[0] != B:
+        raise BlindnoError("psi0 and V batch sizes differ")
+    g = np.broadcast_to(np.asarray(g, dtype=np.float64), (B,)).copy()
+    kappa = np.broadcast_to(np.asarray(kappa, dtype=np.float64), (B,)).copy()
+    for name, n in zip(("Nx", "Ny", "Nz"), shape):
+        if n & (n - 1) or n < 4 or n > 1024:
+            raise BlindnoError(f"{name} = {n}: the {dim}D solver needs a power of two in [4, 1024]")
+    if dim == 3 and int(np.prod(shape)) > 1 << 24:      # the 2D entries set no cell limit
+        raise BlindnoError(f"{' x '.join(str(n) for n in shape)} cells: the 3D solver takes at most 2^24 per trajectory")
+    if order not in (2, 4):
+        raise BlindnoError(f"order = {order}: the solver has orders 2 and 4")
+    if int(rec_every) < 1:
+        raise BlindnoError(f"rec_every = {rec_every}: must be at least 1")
+    return grids, shape, psi0, batched, g, kappa, V
+
+
+def _upload(dev, psi0, V, g, kappa):
+    # fresh C-ordered copies: the inputs may be read-only or broadcast views
+    p0 = torch.from_numpy(np.array(psi0, order="C").view(np.float64)).to(dev)
+    Vd = torch.from_numpy(np.array(V, order="C")).to(dev)
+    return p0, Vd, torch.from_numpy(g).to(dev), torch.from_numpy(kappa).to(dev)
+
+
+def _solve_batch_nd(psi0, grids, dt, t_final, order, g, kappa, V, rec_every, want_abs, want_psi, abs_dtype,
+                    device, max_launches):
+    grids, shape, psi0, batched, g, kappa, V = _problem_nd(psi0, grids, g, kappa, V, order, rec_every)
+    dim, B, cells = len(grids), V.shape[0], int(np.prod(shape))
+    if abs_dtype not in (torch.float64, torch.float32):
+        raise BlindnoError(f"abs_dtype = {abs_dtype}: |psi| is recorded in float64 or float32")
+    nt = int(t_final / dt) + 1
+    nsteps = nt - 1
+    nrec = nsteps // int(rec_every) + 1
+    launches = query(f"blindno_gpe{dim}d_launches", nsteps, int(order))
+    if launches > max_launches:
+        raise BlindnoError(
+            f"{nsteps} steps of order {order} are {launches} kernel launches (limit MAX_LAUNCHES_{dim}D = "
+            f"{max_launches}); refusing to launch -- integrate in several calls, continuing from 'final'")
+    abs_bytes = 8 if abs_dtype == torch.float64 else 4
+    rec_bytes = B * nrec * cells * ((abs_bytes if want_abs else 0) + (16 if want_psi else 0))
+    if rec_bytes > MAX_RECORD_BYTES:
+        raise BlindnoError(
+            f"the record of {B} trajectories x {nrec} frames x {' x '.join(str(n) for n in shape)} is {rec_bytes} "
+            f"bytes (limit MAX_RECORD_BYTES = {MAX_RECORD_BYTES}); refusing to launch -- raise rec_every, record "
+            f"float32 |psi| or solve fewer trajectories per call")
+    dev = _dev(device)
+    t_full = np.linspace(0, t_final, nt)
+    p0, Vd, gd, kd = _upload(dev, psi0, V, g, kappa)
+    rabs = torch.empty(B, nrec, *shape, dtype=abs_dtype, device=dev) if want_abs else None
+    rpsi = torch.empty(B, nrec, *shape, 2, dtype=F64, device=dev) if want_psi else None
+    fin = torch.empty(B, *shape, 2, dtype=F64, device=dev)
+    scratch = torch.empty(query(f"blindno_gpe{dim}d_scratch_doubles", B, *shape), dtype=F64, device=dev)
+    call(f"blindno_gpe{dim}d_solve", ptr(p0), ptr(Vd), ptr(gd), ptr(kd), *(float(a[1] - a[0]) for a in grids),
+         float(dt), nsteps, int(order), int(rec_every), ptr(rabs), int(abs_dtype == torch.float32), ptr(rpsi),
+         ptr(fin), ptr(scratch), B, *shape, int(batched), stream_ptr(dev))
+    out = {"t": t_full[::rec_every][:nrec], "final": torch.view_as_complex(fin)}
+    if want_abs:
+        out["abs"] = rabs
+    if want_psi:
+        out["psi"] = torch.view_as_complex(rpsi)
+    return out
+
+
+def _solve_error_batch_nd(psi0, grids, dt, t_final, order, g, kappa, V, group, rec_every, device, max_launches):
+    grids, shape, psi0, batched, g, kappa, V = _problem_nd(psi0, grids, g, kappa, V, order, rec_every)
+    dim, B = len(grids), V.shape[0]
+    group = B if group is None else int(group)
+    if group < 1 or B % group:
+        raise BlindnoError(f"{B} trajectories are not whole groups of {group}")
+    nt = int(t_final / dt) + 1
+    nsteps = nt - 1
+    nrec = nsteps // int(rec_every) + 1
+    launches = query(f"blindno_gpe{dim}d_error_launches", nsteps, int(order), int(rec_every))
+    if launches > max_launches:
+        raise BlindnoError(
+            f"{nsteps} steps of order {order} with {nrec} reduced frames are {launches} kernel launches (limit "
+            f"MAX_LAUNCHES_{dim}D = {max_launches}); refusing to launch -- raise rec_every or shorten t_final")
+    doubles = query(f"blindno_gpe{dim}d_error_scratch_doubles", B, *shape)
+    if 8 * doubles > MAX_RECORD_BYTES:
+        raise BlindnoError(
+            f"the scratch of {B} trajectories x {' x '.join(str(n) for n in shape)} is {8 * doubles} bytes (limit "
+            f"MAX_RECORD_BYTES = {MAX_RECORD_BYTES}); refusing to launch -- solve fewer groups per call")
+    dev = _dev(device)
+    t_full = np.linspace(0, t_final, nt)
+    p0, Vd, gd, kd = _upload(dev, psi0, V, g, kappa)
+    gridsd = [torch.from_numpy(np.array(a)).to(dev) for a in grids]
+    err = torch.empty(B, nrec, 2, dtype=F64, device=dev)
+    scratch = torch.empty(doubles, dtype=F64, device=dev)
+    call(f"blindno_gpe{dim}d_error", ptr(p0), ptr(Vd), ptr(gd), ptr(kd), *(ptr(a) for a in gridsd),
+         *(float(a[1] - a[0]) for a in grids), float(dt), nsteps, int(order), int(rec_every), group, ptr(err),
+         ptr(scratch), B, *shape, int(batched), stream_ptr(dev))
+    return {"t": t_full[::rec_every][:nrec], "num": err[:, :, 0], "den": err[:, :, 1]}
+
+
+def _time_averaged_L2_error_nd(dim, time_ref, rho_ref, time_pred, rho_pred, grid, eps, device):
+    axes = "xyz"[:dim]
+    dev = _dev(device if device is not None else (rho_ref.device if torch.is_tensor(rho_ref) else None))
+    if tuple(rho_ref.shape) != tuple(rho_pred.shape) or len(rho_ref.shape) != dim + 1:
+        raise ValueError(f"rho_ref shape {tuple(rho_ref.shape)} / rho_pred shape {tuple(rho_pred.shape)}: "
+                         f"expected two equal (Nt, {', '.join('N' + a for a in axes)}) arrays")
+    if not isinstance(grid, (list, tuple)) or len(grid) != dim:
+        raise ValueError(f"grid must be ({', '.join(axes)})")
+    gs = [np.asarray(a, dtype=np.float64).reshape(-1) for a in grid]
+    nt, *shape = (int(v) for v in rho_ref.shape)
+    if [len(a) for a in gs] != shape:
+        raise ValueError(f"grid sizes {tuple(len(a) for a in gs)} do not match the frames {tuple(shape)}")
+    if not np.allclose(np.asarray(time_ref), np.asarray(time_pred)):
+        raise ValueError("time_ref and time_pred differ")
+
+    def d64(a):
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a))
+        return t.to(dev, F64).contiguous()
+
+    a, b = d64(rho_pred), d64(rho_ref)
+    gsd = [d64(a_) for a_ in gs]
+    s = torch.empty(nt, 2, dtype=F64, device=dev)
+    call(f"blindno_trapz{dim}_frames", ptr(a), ptr(b), *(ptr(a_) for a_ in gsd), ptr(s), nt, *shape, stream_ptr(dev))
+    return time_averaged_L2_error_from_sums(d64(time_ref), s[:, 0], s[:, 1], eps)
+
+
+def time_averaged_L2_error_from_sums(t, num, den, eps: float = 1e-12) -> float:
+    """The end of ``time_averaged_L2_error_2d`` / ``_3d``, shared with the record-free path: from the
+    per-time integrals num = trapz((rho_pred - rho_ref)^2) and den = trapz(rho_ref^2), (Nt,) each,
+    rel = sqrt(max(num, 0)) / (sqrt(max(den, 0)) + eps), then the trapezoid time average of rel over
+    ``t`` divided by (t_end - t_0).  ``num`` / ``den`` are fp64 tensors (on any device) or arrays;
+    ``t`` is brought to their device."""
+    num = num if torch.is_tensor(num) else torch.from_numpy(np.asarray(num, dtype=np.float64))
+    den = den if torch.is_tensor(den) else torch.from_numpy(np.asarray(den, dtype=np.float64))
+    t = t if torch.is_tensor(t) else torch.from_numpy(np.asarray(t, dtype=np.float64))
+    t = t.to(num.device, F64)
+    rel = num.clamp_min(0).sqrt() / (den.clamp_min(0).sqrt() + eps)
+    integral = (0.5 * (rel[:-1] + rel[1:]) * (t[1:] - t[:-1])).sum()
+    return float(integral / (t[-1] - t[0]))
+
+
+# ------------------------------------------------------------------------------------- 2D
 
 def solve_batch_2d(psi0, x, y, dt: float, t_final: float, order: int, g, kappa, V,
                    rec_every: int = 1, want_abs: bool = True, want_psi: bool = False,
@@ -199,67 +360,8 @@ def solve_batch_2d(psi0, x, y, dt: float, t_final: float, order: int, g, kappa, 
 
     Refused before anything is launched (BlindnoError): a request of more than MAX_LAUNCHES_2D
     kernel launches, a record above MAX_RECORD_BYTES, and whatever blindno_gpe2d_solve refuses."""
-    x = np.asarray(x, dtype=np.float64)
-    y = np.asarray(y, dtype=np.float64)
-    nx, ny = len(x), len(y)
-    V = np.asarray(V, dtype=np.float64)
-    if V.ndim == 2:
-        V = V[None]
-    if V.ndim != 3 or V.shape[1:] != (nx, ny):
-        raise BlindnoError(f"V has shape {V.shape}; expected (B, {nx}, {ny}) or ({nx}, {ny})")
-    B = V.shape[0]
-    psi0 = np.asarray(psi0, dtype=np.complex128)
-    batched = psi0.ndim == 3
-    if psi0.shape[-2:] != (nx, ny) or psi0.ndim not in (2, 3):
-        raise BlindnoError(f"psi0 has shape {psi0.shape}; expected (B, {nx}, {ny}) or ({nx}, {ny})")
-    if batched and psi0.shape[0] != B:
-        raise BlindnoError("psi0 and V batch sizes differ")
-    g = np.broadcast_to(np.asarray(g, dtype=np.float64), (B,)).copy()
-    kappa = np.broadcast_to(np.asarray(kappa, dtype=np.float64), (B,)).copy()
-    for name, n in (("Nx", nx), ("Ny", ny)):
-        if n & (n - 1) or n < 4 or n > 1024:
-            raise BlindnoError(f"{name} = {n}: the 2D solver needs a power of two in [4, 1024]")
-    if order not in (2, 4):
-        raise BlindnoError(f"order = {order}: the solver has orders 2 and 4")
-    if int(rec_every) < 1:
-        raise BlindnoError(f"rec_every = {rec_every}: must be at least 1")
-    if abs_dtype not in (torch.float64, torch.float32):
-        raise BlindnoError(f"abs_dtype = {abs_dtype}: |psi| is recorded in float64 or float32")
-    nt = int(t_final / dt) + 1
-    nsteps = nt - 1
-    nrec = nsteps // int(rec_every) + 1
-    launches = query("blindno_gpe2d_launches", nsteps, int(order))
-    if launches > MAX_LAUNCHES_2D:
-        raise BlindnoError(
-            f"{nsteps} steps of order {order} are {launches} kernel launches (limit MAX_LAUNCHES_2D = "
-            f"{MAX_LAUNCHES_2D}); refusing to launch -- integrate in several calls, continuing from 'final'")
-    abs_bytes = 8 if abs_dtype == torch.float64 else 4
-    rec_bytes = B * nrec * nx * ny * ((abs_bytes if want_abs else 0) + (16 if want_psi else 0))
-    if rec_bytes > MAX_RECORD_BYTES:
-        raise BlindnoError(
-            f"the record of {B} trajectories x {nrec} frames x {nx} x {ny} is {rec_bytes} bytes (limit "
-            f"MAX_RECORD_BYTES = {MAX_RECORD_BYTES}); refusing to launch -- raise rec_every, record float32 "
-            f"|psi| or solve fewer trajectories per call")
-    dev = _dev(device)
-    t_full = np.linspace(0, t_final, nt)
-    # fresh C-ordered copies: the inputs may be read-only or broadcast views
-    p0 = torch.from_numpy(np.array(psi0, order="C").view(np.float64)).to(dev)
-    Vd = torch.from_numpy(np.array(V, order="C")).to(dev)
-    gd = torch.from_numpy(g).to(dev)
-    kd = torch.from_numpy(kappa).to(dev)
-    rabs = torch.empty(B, nrec, nx, ny, dtype=abs_dtype, device=dev) if want_abs else None
-    rpsi = torch.empty(B, nrec, nx, ny, 2, dtype=F64, device=dev) if want_psi else None
-    fin = torch.empty(B, nx, ny, 2, dtype=F64, device=dev)
-    scratch = torch.empty(query("blindno_gpe2d_scratch_doubles", B, nx, ny), dtype=F64, device=dev)
-    call("blindno_gpe2d_solve", ptr(p0), ptr(Vd), ptr(gd), ptr(kd), float(x[1] - x[0]), float(y[1] - y[0]),
-         float(dt), nsteps, int(order), int(rec_every), ptr(rabs), int(abs_dtype == torch.float32), ptr(rpsi),
-         ptr(fin), ptr(scratch), B, nx, ny, int(batched), stream_ptr(dev))
-    out = {"t": t_full[::rec_every][:nrec], "final": torch.view_as_complex(fin)}
-    if want_abs:
-        out["abs"] = rabs
-    if want_psi:
-        out["psi"] = torch.view_as_complex(rpsi)
-    return out
+    return _solve_batch_nd(psi0, (x, y), dt, t_final, order, g, kappa, V, rec_every, want_abs, want_psi, abs_dtype,
+                           device, MAX_LAUNCHES_2D)
 
 
 def training_potentials_2d(num_orbits: int, x: np.ndarray, y: np.ndarray, rng=np.random) -> np.ndarray:
@@ -312,30 +414,7 @@ def time_averaged_L2_error_2d(time_ref, rho_ref, time_pred, rho_pred, grid, eps:
     sqrt(trapz_y(trapz_x((rho_pred - rho_ref)^2))) / (sqrt(trapz_y(trapz_x(rho_ref^2))) + eps),
     then the trapezoid time average / (t_end - t_0).  rho_* are numpy arrays or device tensors;
     the spatial integrals run on the GPU in fp64 (blindno_trapz2_frames)."""
-    dev = _dev(device if device is not None else (rho_ref.device if torch.is_tensor(rho_ref) else None))
-    if tuple(rho_ref.shape) != tuple(rho_pred.shape) or len(rho_ref.shape) != 3:
-        raise ValueError(f"rho_ref shape {tuple(rho_ref.shape)} / rho_pred shape {tuple(rho_pred.shape)}: "
-                         "expected two equal (Nt, Nx, Ny) arrays")
-    if not isinstance(grid, (list, tuple)) or len(grid) != 2:
-        raise ValueError("grid must be (x, y)")
-    xg, yg = (np.asarray(a, dtype=np.float64).reshape(-1) for a in grid)
-    nt, nx, ny = (int(v) for v in rho_ref.shape)
-    if (len(xg), len(yg)) != (nx, ny):
-        raise ValueError(f"grid sizes {(len(xg), len(yg))} do not match the frames {(nx, ny)}")
-    if not np.allclose(np.asarray(time_ref), np.asarray(time_pred)):
-        raise ValueError("time_ref and time_pred differ")
-
-    def d64(a):
-        t = a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a))
-        return t.to(dev, F64).contiguous()
-
-    a, b = d64(rho_pred), d64(rho_ref)
-    s = torch.empty(nt, 2, dtype=F64, device=dev)
-    call("blindno_trapz2_frames", ptr(a), ptr(b), ptr(d64(xg)), ptr(d64(yg)), ptr(s), nt, nx, ny, stream_ptr(dev))
-    rel = s[:, 0].clamp_min(0).sqrt() / (s[:, 1].clamp_min(0).sqrt() + eps)
-    t = d64(time_ref)
-    integral = (0.5 * (rel[:-1] + rel[1:]) * (t[1:] - t[:-1])).sum()
-    return float(integral / (t[-1] - t[0]))
+    return _time_averaged_L2_error_nd(2, time_ref, rho_ref, time_pred, rho_pred, grid, eps, device)
 
 
 def solve_error_batch_2d(psi0, x, y, dt: float, t_final: float, order: int, g, kappa, V,
@@ -355,73 +434,11 @@ def solve_error_batch_2d(psi0, x, y, dt: float, t_final: float, order: int, g, k
     Refused before anything is launched (BlindnoError): a batch that is not whole groups, more than
     MAX_LAUNCHES_2D kernel launches (blindno_gpe2d_error_launches: the solver's plus two per recorded
     step), scratch above MAX_RECORD_BYTES, and whatever blindno_gpe2d_error refuses."""
-    x = np.asarray(x, dtype=np.float64)
-    y = np.asarray(y, dtype=np.float64)
-    nx, ny = len(x), len(y)
-    V = np.asarray(V, dtype=np.float64)
-    if V.ndim == 2:
-        V = V[None]
-    if V.ndim != 3 or V.shape[1:] != (nx, ny):
-        raise BlindnoError(f"V has shape {V.shape}; expected (B, {nx}, {ny}) or ({nx}, {ny})")
-    B = V.shape[0]
-    psi0 = np.asarray(psi0, dtype=np.complex128)
-    batched = psi0.ndim == 3
-    if psi0.shape[-2:] != (nx, ny) or psi0.ndim not in (2, 3):
-        raise BlindnoError(f"psi0 has shape {psi0.shape}; expected (B, {nx}, {ny}) or ({nx}, {ny})")
-    if batched and psi0.shape[0] != B:
-        raise BlindnoError("psi0 and V batch sizes differ")
-    g = np.broadcast_to(np.asarray(g, dtype=np.float64), (B,)).copy()
-    kappa = np.broadcast_to(np.asarray(kappa, dtype=np.float64), (B,)).copy()
-    for name, n in (("Nx", nx), ("Ny", ny)):
-        if n & (n - 1) or n < 4 or n > 1024:
-            raise BlindnoError(f"{name} = {n}: the 2D solver needs a power of two in [4, 1024]")
-    if order not in (2, 4):
-        raise BlindnoError(f"order = {order}: the solver has orders 2 and 4")
-    if int(rec_every) < 1:
-        raise BlindnoError(f"rec_every = {rec_every}: must be at least 1")
-    group = B if group is None else int(group)
-    if group < 1 or B % group:
-        raise BlindnoError(f"{B} trajectories are not whole groups of {group}")
-    nt = int(t_final / dt) + 1
-    nsteps = nt - 1
-    nrec = nsteps // int(rec_every) + 1
-    launches = query("blindno_gpe2d_error_launches", nsteps, int(order), int(rec_every))
-    if launches > MAX_LAUNCHES_2D:
-        raise BlindnoError(
-            f"{nsteps} steps of order {order} with {nrec} reduced frames are {launches} kernel launches (limit "
-            f"MAX_LAUNCHES_2D = {MAX_LAUNCHES_2D}); refusing to launch -- raise rec_every or shorten t_final")
-    doubles = query("blindno_gpe2d_error_scratch_doubles", B, nx, ny)
-    if 8 * doubles > MAX_RECORD_BYTES:
-        raise BlindnoError(
-            f"the scratch of {B} trajectories x {nx} x {ny} is {8 * doubles} bytes (limit MAX_RECORD_BYTES = "
-            f"{MAX_RECORD_BYTES}); refusing to launch -- solve fewer groups per call")
-    dev = _dev(device)
-    t_full = np.linspace(0, t_final, nt)
-    # fresh C-ordered copies: the inputs may be read-only or broadcast views
-    p0 = torch.from_numpy(np.array(psi0, order="C").view(np.float64)).to(dev)
-    Vd = torch.from_numpy(np.array(V, order="C")).to(dev)
-    gd = torch.from_numpy(g).to(dev)
-    kd = torch.from_numpy(kappa).to(dev)
-    xd, yd = (torch.from_numpy(np.array(a)).to(dev) for a in (x, y))
-    err = torch.empty(B, nrec, 2, dtype=F64, device=dev)
-    scratch = torch.empty(doubles, dtype=F64, device=dev)
-    call("blindno_gpe2d_error", ptr(p0), ptr(Vd), ptr(gd), ptr(kd), ptr(xd), ptr(yd), float(x[1] - x[0]),
-         float(y[1] - y[0]), float(dt), nsteps, int(order), int(rec_every), group, ptr(err), ptr(scratch), B, nx, ny,
-         int(batched), stream_ptr(dev))
-    return {"t": t_full[::rec_every][:nrec], "num": err[:, :, 0], "den": err[:, :, 1]}
+    return _solve_error_batch_nd(psi0, (x, y), dt, t_final, order, g, kappa, V, group, rec_every, device,
+                                 MAX_LAUNCHES_2D)
 
 
 # ------------------------------------------------------------------------------------- 3D
-# The project's own, like the 2D functions above: the same scheme on three axes (csrc/gpe3d.hip,
-# grid-resident; every kinetic step is a z launch, a y launch and an x launch).
-
-# The launches one solve_batch_3d call may enqueue (3 per Strang step, 12 per Yoshida step).  The
-# rule of MAX_LAUNCHES_2D: the largest power of two whose worst case stays under 120 s at the time
-# per launch measured by tools/bench_gpe3d.py at its headline shape, 64^3 with B = 16
-# (profiles/gpe3d_bench.json: 77.39 us per launch; 120 s / 77.39 us = 1.55 M, 2^20 launches take
-# 81.1 s and 2^21 would take 162.3 s; DESIGN 4c).
-MAX_LAUNCHES_3D = 1 << 20
-
 
 def solve_batch_3d(psi0, x, y, z, dt: float, t_final: float, order: int, g, kappa, V,
                    rec_every: int = 1, want_abs: bool = True, want_psi: bool = False,
@@ -438,72 +455,8 @@ def solve_batch_3d(psi0, x, y, z, dt: float, t_final: float, order: int, g, kapp
 
     Refused before anything is launched (BlindnoError): a request of more than MAX_LAUNCHES_3D
     kernel launches, a record above MAX_RECORD_BYTES, and whatever blindno_gpe3d_solve refuses."""
-    x = np.asarray(x, dtype=np.float64)
-    y = np.asarray(y, dtype=np.float64)
-    z = np.asarray(z, dtype=np.float64)
-    shape = (len(x), len(y), len(z))
-    nx, ny, nz = shape
-    V = np.asarray(V, dtype=np.float64)
-    if V.ndim == 3:
-        V = V[None]
-    if V.ndim != 4 or V.shape[1:] != shape:
-        raise BlindnoError(f"V has shape {V.shape}; expected (B, {nx}, {ny}, {nz}) or ({nx}, {ny}, {nz})")
-    B = V.shape[0]
-    psi0 = np.asarray(psi0, dtype=np.complex128)
-    batched = psi0.ndim == 4
-    if psi0.shape[-3:] != shape or psi0.ndim not in (3, 4):
-        raise BlindnoError(f"psi0 has shape {psi0.shape}; expected (B, {nx}, {ny}, {nz}) or ({nx}, {ny}, {nz})")
-    if batched and psi0.shape[0] != B:
-        raise BlindnoError("psi0 and V batch sizes differ")
-    g = np.broadcast_to(np.asarray(g, dtype=np.float64), (B,)).copy()
-    kappa = np.broadcast_to(np.asarray(kappa, dtype=np.float64), (B,)).copy()
-    for name, n in (("Nx", nx), ("Ny", ny), ("Nz", nz)):
-        if n & (n - 1) or n < 4 or n > 1024:
-            raise BlindnoError(f"{name} = {n}: the 3D solver needs a power of two in [4, 1024]")
-    if nx * ny * nz > 1 << 24:
-        raise BlindnoError(f"{nx} x {ny} x {nz} cells: the 3D solver takes at most 2^24 per trajectory")
-    if order not in (2, 4):
-        raise BlindnoError(f"order = {order}: the solver has orders 2 and 4")
-    if int(rec_every) < 1:
-        raise BlindnoError(f"rec_every = {rec_every}: must be at least 1")
-    if abs_dtype not in (torch.float64, torch.float32):
-        raise BlindnoError(f"abs_dtype = {abs_dtype}: |psi| is recorded in float64 or float32")
-    nt = int(t_final / dt) + 1
-    nsteps = nt - 1
-    nrec = nsteps // int(rec_every) + 1
-    launches = query("blindno_gpe3d_launches", nsteps, int(order))
-    if launches > MAX_LAUNCHES_3D:
-        raise BlindnoError(
-            f"{nsteps} steps of order {order} are {launches} kernel launches (limit MAX_LAUNCHES_3D = "
-            f"{MAX_LAUNCHES_3D}); refusing to launch -- integrate in several calls, continuing from 'final'")
-    abs_bytes = 8 if abs_dtype == torch.float64 else 4
-    rec_bytes = B * nrec * nx * ny * nz * ((abs_bytes if want_abs else 0) + (16 if want_psi else 0))
-    if rec_bytes > MAX_RECORD_BYTES:
-        raise BlindnoError(
-            f"the record of {B} trajectories x {nrec} frames x {nx} x {ny} x {nz} is {rec_bytes} bytes (limit "
-            f"MAX_RECORD_BYTES = {MAX_RECORD_BYTES}); refusing to launch -- raise rec_every, record float32 "
-            f"|psi| or solve fewer trajectories per call")
-    dev = _dev(device)
-    t_full = np.linspace(0, t_final, nt)
-    # fresh C-ordered copies: the inputs may be read-only or broadcast views
-    p0 = torch.from_numpy(np.array(psi0, order="C").view(np.float64)).to(dev)
-    Vd = torch.from_numpy(np.array(V, order="C")).to(dev)
-    gd = torch.from_numpy(g).to(dev)
-    kd = torch.from_numpy(kappa).to(dev)
-    rabs = torch.empty(B, nrec, nx, ny, nz, dtype=abs_dtype, device=dev) if want_abs else None
-    rpsi = torch.empty(B, nrec, nx, ny, nz, 2, dtype=F64, device=dev) if want_psi else None
-    fin = torch.empty(B, nx, ny, nz, 2, dtype=F64, device=dev)
-    scratch = torch.empty(query("blindno_gpe3d_scratch_doubles", B, nx, ny, nz), dtype=F64, device=dev)
-    call("blindno_gpe3d_solve", ptr(p0), ptr(Vd), ptr(gd), ptr(kd), float(x[1] - x[0]), float(y[1] - y[0]),
-         float(z[1] - z[0]), float(dt), nsteps, int(order), int(rec_every), ptr(rabs),
-         int(abs_dtype == torch.float32), ptr(rpsi), ptr(fin), ptr(scratch), B, nx, ny, nz, int(batched),
-         stream_ptr(dev))
-    out = {"t": t_full[::rec_every][:nrec], "final": torch.view_as_complex(fin)}
-    if want_abs:
-        out["abs"] = rabs
-    if want_psi:
-        out["psi"] = torch.view_as_complex(rpsi)
-    return out
+    return _solve_batch_nd(psi0, (x, y, z), dt, t_final, order, g, kappa, V, rec_every, want_abs, want_psi,
+                           abs_dtype, device, MAX_LAUNCHES_3D)
 
 
 def training_potentials_3d(num_orbits: int, x: np.ndarray, y: np.ndarray, z: np.ndarray,
@@ -561,43 +514,7 @@ def time_averaged_L2_error_3d(time_ref, rho_ref, time_pred, rho_pred, grid, eps:
     time sqrt(trapz_z(trapz_y(trapz_x((rho_pred - rho_ref)^2)))) / (sqrt(the same of rho_ref^2) +
     eps), then the trapezoid time average / (t_end - t_0).  rho_* are numpy arrays or device
     tensors; the spatial integrals run on the GPU in fp64 (blindno_trapz3_frames)."""
-    dev = _dev(device if device is not None else (rho_ref.device if torch.is_tensor(rho_ref) else None))
-    if tuple(rho_ref.shape) != tuple(rho_pred.shape) or len(rho_ref.shape) != 4:
-        raise ValueError(f"rho_ref shape {tuple(rho_ref.shape)} / rho_pred shape {tuple(rho_pred.shape)}: "
-                         "expected two equal (Nt, Nx, Ny, Nz) arrays")
-    if not isinstance(grid, (list, tuple)) or len(grid) != 3:
-        raise ValueError("grid must be (x, y, z)")
-    xg, yg, zg = (np.asarray(a, dtype=np.float64).reshape(-1) for a in grid)
-    nt, nx, ny, nz = (int(v) for v in rho_ref.shape)
-    if (len(xg), len(yg), len(zg)) != (nx, ny, nz):
-        raise ValueError(f"grid sizes {(len(xg), len(yg), len(zg))} do not match the frames {(nx, ny, nz)}")
-    if not np.allclose(np.asarray(time_ref), np.asarray(time_pred)):
-        raise ValueError("time_ref and time_pred differ")
-
-    def d64(a):
-        t = a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a))
-        return t.to(dev, F64).contiguous()
-
-    a, b = d64(rho_pred), d64(rho_ref)
-    s = torch.empty(nt, 2, dtype=F64, device=dev)
-    call("blindno_trapz3_frames", ptr(a), ptr(b), ptr(d64(xg)), ptr(d64(yg)), ptr(d64(zg)), ptr(s), nt, nx, ny, nz,
-         stream_ptr(dev))
-    return time_averaged_L2_error_from_sums(d64(time_ref), s[:, 0], s[:, 1], eps)
-
-
-def time_averaged_L2_error_from_sums(t, num, den, eps: float = 1e-12) -> float:
-    """The end of ``time_averaged_L2_error_3d``, shared with the record-free path: from the per-time
-    integrals num = trapz((rho_pred - rho_ref)^2) and den = trapz(rho_ref^2), (Nt,) each,
-    rel = sqrt(max(num, 0)) / (sqrt(max(den, 0)) + eps), then the trapezoid time average of rel over
-    ``t`` divided by (t_end - t_0).  ``num`` / ``den`` are fp64 tensors (on any device) or arrays;
-    ``t`` is brought to their device."""
-    num = num if torch.is_tensor(num) else torch.from_numpy(np.asarray(num, dtype=np.float64))
-    den = den if torch.is_tensor(den) else torch.from_numpy(np.asarray(den, dtype=np.float64))
-    t = t if torch.is_tensor(t) else torch.from_numpy(np.asarray(t, dtype=np.float64))
-    t = t.to(num.device, F64)
-    rel = num.clamp_min(0).sqrt() / (den.clamp_min(0).sqrt() + eps)
-    integral = (0.5 * (rel[:-1] + rel[1:]) * (t[1:] - t[:-1])).sum()
-    return float(integral / (t[-1] - t[0]))
+    return _time_averaged_L2_error_nd(3, time_ref, rho_ref, time_pred, rho_pred, grid, eps, device)
 
 
 def solve_error_batch_3d(psi0, x, y, z, dt: float, t_final: float, order: int, g, kappa, V,
@@ -616,61 +533,5 @@ def solve_error_batch_3d(psi0, x, y, z, dt: float, t_final: float, order: int, g
     Refused before anything is launched (BlindnoError): a batch that is not whole groups, more than
     MAX_LAUNCHES_3D kernel launches (blindno_gpe3d_error_launches: the solver's plus two per recorded
     step), scratch above MAX_RECORD_BYTES, and whatever blindno_gpe3d_error refuses."""
-    x = np.asarray(x, dtype=np.float64)
-    y = np.asarray(y, dtype=np.float64)
-    z = np.asarray(z, dtype=np.float64)
-    shape = (len(x), len(y), len(z))
-    nx, ny, nz = shape
-    V = np.asarray(V, dtype=np.float64)
-    if V.ndim == 3:
-        V = V[None]
-    if V.ndim != 4 or V.shape[1:] != shape:
-        raise BlindnoError(f"V has shape {V.shape}; expected (B, {nx}, {ny}, {nz}) or ({nx}, {ny}, {nz})")
-    B = V.shape[0]
-    psi0 = np.asarray(psi0, dtype=np.complex128)
-    batched = psi0.ndim == 4
-    if psi0.shape[-3:] != shape or psi0.ndim not in (3, 4):
-        raise BlindnoError(f"psi0 has shape {psi0.shape}; expected (B, {nx}, {ny}, {nz}) or ({nx}, {ny}, {nz})")
-    if batched and psi0.shape[0] != B:
-        raise BlindnoError("psi0 and V batch sizes differ")
-    g = np.broadcast_to(np.asarray(g, dtype=np.float64), (B,)).copy()
-    kappa = np.broadcast_to(np.asarray(kappa, dtype=np.float64), (B,)).copy()
-    for name, n in (("Nx", nx), ("Ny", ny), ("Nz", nz)):
-        if n & (n - 1) or n < 4 or n > 1024:
-            raise BlindnoError(f"{name} = {n}: the 3D solver needs a power of two in [4, 1024]")
-    if nx * ny * nz > 1 << 24:
-        raise BlindnoError(f"{nx} x {ny} x {nz} cells: the 3D solver takes at most 2^24 per trajectory")
-    if order not in (2, 4):
-        raise BlindnoError(f"order = {order}: the solver has orders 2 and 4")
-    if int(rec_every) < 1:
-        raise BlindnoError(f"rec_every = {rec_every}: must be at least 1")
-    group = B if group is None else int(group)
-    if group < 1 or B % group:
-        raise BlindnoError(f"{B} trajectories are not whole groups of {group}")
-    nt = int(t_final / dt) + 1
-    nsteps = nt - 1
-    nrec = nsteps // int(rec_every) + 1
-    launches = query("blindno_gpe3d_error_launches", nsteps, int(order), int(rec_every))
-    if launches > MAX_LAUNCHES_3D:
-        raise BlindnoError(
-            f"{nsteps} steps of order {order} with {nrec} reduced frames are {launches} kernel launches (limit "
-            f"MAX_LAUNCHES_3D = {MAX_LAUNCHES_3D}); refusing to launch -- raise rec_every or shorten t_final")
-    doubles = query("blindno_gpe3d_error_scratch_doubles", B, nx, ny, nz)
-    if 8 * doubles > MAX_RECORD_BYTES:
-        raise BlindnoError(
-            f"the scratch of {B} trajectories x {nx} x {ny} x {nz} is {8 * doubles} bytes (limit MAX_RECORD_BYTES = "
-            f"{MAX_RECORD_BYTES}); refusing to launch -- solve fewer groups per call")
-    dev = _dev(device)
-    t_full = np.linspace(0, t_final, nt)
-    # fresh C-ordered copies: the inputs may be read-only or broadcast views
-    p0 = torch.from_numpy(np.array(psi0, order="C").view(np.float64)).to(dev)
-    Vd = torch.from_numpy(np.array(V, order="C")).to(dev)
-    gd = torch.from_numpy(g).to(dev)
-    kd = torch.from_numpy(kappa).to(dev)
-    xd, yd, zd = (torch.from_numpy(np.array(a)).to(dev) for a in (x, y, z))
-    err = torch.empty(B, nrec, 2, dtype=F64, device=dev)
-    scratch = torch.empty(doubles, dtype=F64, device=dev)
-    call("blindno_gpe3d_error", ptr(p0), ptr(Vd), ptr(gd), ptr(kd), ptr(xd), ptr(yd), ptr(zd),
-         float(x[1] - x[0]), float(y[1] - y[0]), float(z[1] - z[0]), float(dt), nsteps, int(order), int(rec_every),
-         group, ptr(err), ptr(scratch), B, nx, ny, nz, int(batched), stream_ptr(dev))
-    return {"t": t_full[::rec_every][:nrec], "num": err[:, :, 0], "den": err[:, :, 1]}
+    return _solve_error_batch_nd(psi0, (x, y, z), dt, t_final, order, g, kappa, V, group, rec_every, device,
+                                 MAX_LAUNCHES_3D)

@@ -58,9 +58,9 @@ def test_gpe3d_symbols_declared_and_bound():
     n = lambda *a: _lib.query("blindno_gpe3d_launches", *a)          # noqa: E731
     assert (n(1000, 2), n(1000, 4), n(0, 2), n(0, 4), n(5, 3), n(-1, 2)) == (3000, 12000, 1, 1, -1, -1)
     csrc = os.path.join(ROOT, "reconstruction-of-pde-without-time-label_amd", "csrc")
-    src = open(os.path.join(csrc, "gpe3d.hip")).read()
+    src = open(os.path.join(csrc, "gpe_nd.hip")).read()
     assert "atomic" not in src.lower() and "hipLaunchCooperativeKernel" not in src
-    assert "gpe3d.hip" in [os.path.basename(p) for p in glob.glob(os.path.join(csrc, "*.hip"))]
+    assert "gpe_nd.hip" in [os.path.basename(p) for p in glob.glob(os.path.join(csrc, "*.hip"))]
 
 
 def _problem2(n1, n2, seed=0):

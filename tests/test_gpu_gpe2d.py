@@ -1,4 +1,4 @@
-"""The grid-resident 2D GPE solver (blindno_gpe2d_solve, csrc/gpe2d.hip), the 2D density error
+"""The grid-resident 2D GPE solver (blindno_gpe2d_solve, csrc/gpe_nd.hip), the 2D density error
 (blindno_trapz2_frames), the generator, the evaluator and the 2d_GPE experiment (needs a GPU).
 
 The checker is tests/gpe2d_ref.py: numpy.fft.fft2 with one 2D phase per kinetic step, where the

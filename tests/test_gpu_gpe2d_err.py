@@ -1,4 +1,4 @@
-"""The record-free 2D GPE density error (blindno_gpe2d_error, csrc/gpe2d.hip; needs a GPU):
+"""The record-free 2D GPE density error (blindno_gpe2d_error, csrc/gpe_nd.hip; needs a GPU):
 gpe.solve_error_batch_2d against the recorded path (solve_batch_2d + blindno_trapz2_frames, both
 unchanged code) and against the numpy checker tests/gpe2d_ref.py, and the record_free path of
 timeerror.compute_time_error_gpe_2d.

@@ -1,4 +1,4 @@
-"""The grid-resident 3D GPE solver (blindno_gpe3d_solve, csrc/gpe3d.hip), the 3D density error
+"""The grid-resident 3D GPE solver (blindno_gpe3d_solve, csrc/gpe_nd.hip), the 3D density error
 (blindno_trapz3_frames), the generator and the evaluator (needs a GPU).
 
 The checker is tests/gpe3d_ref.py: numpy.fft.fftn with one 3D phase per kinetic step, where the

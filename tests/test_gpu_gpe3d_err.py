@@ -1,4 +1,4 @@
-"""The record-free 3D GPE density error (blindno_gpe3d_error, csrc/gpe3d.hip; needs a GPU):
+"""The record-free 3D GPE density error (blindno_gpe3d_error, csrc/gpe_nd.hip; needs a GPU):
 gpe.solve_error_batch_3d against the recorded path (solve_batch_3d + blindno_trapz3_frames, both
 unchanged code) and against the numpy checker tests/gpe3d_ref.py, and the record_free path of
 timeerror.compute_time_error_gpe_3d.

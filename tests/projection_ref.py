@@ -121,8 +121,9 @@ def project_bwd_abs(z, w1, b1, w2, dout, Ho, Wo, dout_div=1, lscale=None):
                        None if lscale is None else np.abs(lscale))
 
 
-def project_bwd_bound(z, w1, b1, w2, dout, Ho, Wo, dout_div=1, lscale=None):
-    """The bounds of (dz, grads), shaped like project_bwd's results."""
+def project_bwd_bound(z, w1, b1, w2, dout, Ho, Wo, dout_div=1, lscale=None, chain=None):
+    """The bounds of (dz, grads), shaped like project_bwd's results.  chain: the accumulation length of
+    the parameter sums where it is not the number of crop points (partial rows added in float64)."""
     z, w1, b1, w2 = _f64(z, w1, b1, w2)
     zc = crop(z, Ho, Wo)
     h = hidden(zc, w1, b1)
@@ -132,7 +133,7 @@ def project_bwd_bound(z, w1, b1, w2, dout, Ho, Wo, dout_div=1, lscale=None):
     dHa = (np.abs(g) @ np.abs(w2)) * np.abs(gelu_grad(h))
     Hd, N = w1.shape[0], zc.shape[0] * Ho * Wo
     dz = (e @ np.abs(w1) + (Hd + C_EXTRA) * U24 * (dHa @ np.abs(w1))).transpose(0, 3, 1, 2)
-    nu = (N + C_EXTRA) * U24
+    nu = ((N if chain is None else chain) + C_EXTRA) * U24
     az, ag = np.abs(zc), np.abs(g)
     grads = np.concatenate([
         (np.einsum("nhwk,nhwc->kc", e, az) + nu * np.einsum("nhwk,nhwc->kc", dHa, az)).ravel(),

@@ -16,6 +16,7 @@ from .encoders import (ConvBlock, ConvBlock3D, Encoder, Encoder2D, Encoder3D,  #
                        Encoder3D_down)
 from .unet import (PermInvUNet_attn, PermInvUNet_attn1D, PermInvUNet_attn1D_bag,  # noqa: F401
                    PermInvUNet_attn1D_bag_GPE, PermInvUNet_attn1D_bag_V, PermInvUNet_attn_NC)
+from .unet3d import PermInvUNet_attn3D  # noqa: F401
 from .ops import mse_loss, pad_amount, set_mix_precision  # noqa: F401
 from . import torch_ops  # noqa: F401  (registers torch.ops.blindno.*)
 

@@ -257,6 +257,22 @@ SIGNATURES_NIOATTN = {
     "blindno_nioattn_bwd": "pppppppppp" + "pppp" + "iiiiii" + "s",
 }
 
+# include/blindno_unet3d.h: the 3D kernels of PermInvUNet_attn3D (csrc/unet3d.hip); depthwise and
+# pool geometry = (N | NC, [C,] D, H, W, KD, KH, KW), transposed conv = (N, Ci, Di, Hi, Wi, Co, Do,
+# Ho, Wo)
+SIGNATURES_UNET3D = {
+    "blindno_dwconv3d_fwd": "pppp" + "i" * 8 + "s",
+    "blindno_dwconv3d_bwd_data": "ppp" + "i" * 8 + "s",
+    "blindno_dwconv3d_wgrad_nsplit": "i" * 8,
+    "blindno_dwconv3d_bwd_weight": "pppp" + "i" + "i" * 8 + "s",
+    "blindno_maxpool3d_fwd": "ppp" + "i" * 7 + "s",
+    "blindno_maxpool3d_bwd": "ppp" + "i" * 7 + "s",
+    "blindno_convt3d_fwd": "pppp" + "i" * 9 + "s",
+    "blindno_convt3d_bwd_data": "ppp" + "i" * 9 + "s",
+    "blindno_convt3d_wgrad_nparts": "iiii",
+    "blindno_convt3d_bwd_weight": "pppp" + "i" * 9 + "s",
+}
+
 # entry points returning int64_t (byte counts) instead of an error code / int count
 RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))} | \
     {n for n in SIGNATURES_GPE3D if n.endswith(("_doubles", "_launches"))} | \
@@ -294,7 +310,7 @@ def load():
         for name, sig in {**SIGNATURES, **SIGNATURES_CONV3D, **SIGNATURES_FPE, **SIGNATURES_GPE2D,
                           **SIGNATURES_BAG3D, **SIGNATURES_GPE3D, **SIGNATURES_FPE_ERR,
                           **SIGNATURES_GPE3D_ERR, **SIGNATURES_GPE2D_ERR,
-                          **SIGNATURES_NIOATTN}.items():
+                          **SIGNATURES_NIOATTN, **SIGNATURES_UNET3D}.items():
             fn = getattr(lib, name)
             fn.argtypes = [_CT[c] for c in sig]
             fn.restype = ctypes.c_int64 if name in RET64 else ctypes.c_int
@@ -308,7 +324,7 @@ def exported_symbols():
     return (list(SIGNATURES) + list(SIGNATURES_CONV3D) + list(SIGNATURES_FPE) + list(SIGNATURES_GPE2D) +
             list(SIGNATURES_BAG3D) + list(SIGNATURES_GPE3D) + list(SIGNATURES_FPE_ERR) +
             list(SIGNATURES_GPE3D_ERR) + list(SIGNATURES_GPE2D_ERR) + list(SIGNATURES_NIOATTN) +
-            ["blindno_error_string"])
+            list(SIGNATURES_UNET3D) + ["blindno_error_string"])
 
 
 def stream_ptr(device=None):

@@ -23,7 +23,8 @@ Reference loops (one per experiment; the flat module-level scripts):
                                             eval every 10, results_GPE_nio/
   the project's own (no reference script): 2d_GPE, and 3d_FPE = NIOFP3D_FNO(2,8,4,2,input_modes=4)
   on datagen.fpe_3d_dataset files, bs 4, lr 5e-4, eval every 5, results_3d_FPE_fno/ -- an eager
-  step (``Experiment.eager``: no graph capture), one process only, --model fno only
+  step (``Experiment.eager``: no graph capture), one process only; --model unet trains
+  PermInvUNet_attn3D(1, 2, 1, 3, (n, n, n)) the same way (results_3d_FPE_unet/); no --model nio
 
 What is kept from the reference, exactly:
   * dataset scaling / z-scoring (``blindno.data``, bit-pinned to the reference classes) and the
@@ -160,6 +161,28 @@ def _experiments(model: str = "fno"):
                              lambda n, dev: nio.NIOFP3D_FNO(2, 8, 4, 2, dev, input_modes=4), 5e-4, 4, 5,
                              "results_3d_FPE_fno", True, all4, ("fc0.",), eager=True),
     }
+
+
+def _own_experiments(model: str = "fno"):
+    """Experiments with a model of the project's own that the reference has no script for and
+    ``_experiments`` (the reference's train_*.py tables, with the NIO-FNO 2d_GPE / 3d_FPE entries)
+    does not hold.  ``model="unet"``: 3d_FPE with PermInvUNet_attn3D(1, 2, 1, 3, (n, n, n)) on
+    datagen.fpe_3d_dataset files -- the 2D UNet entry's lr, batch and eval period, an eager step,
+    one process only, results_3d_FPE_unet/."""
+    if model != "unet":
+        return {}
+    from . import data, unet3d
+    all4 = ("train_losses", "test_losses", "test_losses_drift", "test_losses_diffusion")
+    return {
+        "3d_FPE": Experiment("3d_FPE", 3, data.TrajectoryDataset3D,
+                             lambda n, dev: unet3d.PermInvUNet_attn3D(1, 2, 1, 3, (n, n, n), device=dev),
+                             5e-4, 4, 5, "results_3d_FPE_unet", True, all4, eager=True),
+    }
+
+
+def experiments_for(model: str = "fno"):
+    """Every experiment ``--model`` can train: the reference's tables and the project's own."""
+    return {**_experiments(model), **_own_experiments(model)}
 
 
 def split_indices(n: int, seed: int = SPLIT_SEED):
@@ -355,10 +378,10 @@ def main(argv=None):
     ap.add_argument("--scheduler-mode", choices=["reference", "per-epoch"], default="reference")
     ap.add_argument("--eval-mode", choices=["reference", "global"], default="reference")
     a = ap.parse_args(argv)
-    exps = _experiments(a.model)
+    exps = experiments_for(a.model)
     if a.experiment not in exps:
         ap.error(f"--experiment {a.experiment} has no --model {a.model} configuration "
-                 f"(it has: {', '.join(m for m in ('fno', 'unet', 'nio') if a.experiment in _experiments(m))})")
+                 f"(it has: {', '.join(m for m in ('fno', 'unet', 'nio') if a.experiment in experiments_for(m))})")
     exp = exps[a.experiment]
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))

@@ -903,5 +903,6 @@ int blindno_project3d_bwd(const float* z, const float* w1, const float* b1, cons
 #include "blindno_gpe2d_err.h"
 #include "blindno_nioattn.h"
 #include "blindno_unet3d.h"
+#include "blindno_physattn.h"
 
 #endif /* BLINDNO_H */

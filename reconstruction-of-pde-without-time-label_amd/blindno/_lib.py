@@ -273,6 +273,20 @@ SIGNATURES_UNET3D = {
     "blindno_convt3d_bwd_weight": "pppp" + "i" * 9 + "s",
 }
 
+# include/blindno_physattn.h: physics attention of the structured-mesh Transolver and the LayerNorm
+# over channel planes (csrc/physattn.hip); strides between snapshots are int64
+SIGNATURES_PHYSATTN = {
+    "blindno_physattn_ok": "iiiiii",
+    "blindno_physattn_nblk": "ii",
+    "blindno_physattn_fwd_scratch_floats": "iii",
+    "blindno_physattn_fwd": "pp" + "l" + "ppppppppp" + "ppppppp" + "iii" + "s",
+    "blindno_physattn_bwd_scratch_floats": "iii",
+    "blindno_physattn_bwd": "ppp" + "l" + "ppppppp" + "ppppp" + "ppp" + "l" + "pppppppp" + "iii" + "s",
+    "blindno_ln_planes_nblk": "i",
+    "blindno_ln_planes_fwd": "pppppp" + "iii" + "f" + "s",
+    "blindno_ln_planes_bwd": "ppppppppp" + "iii" + "s",
+}
+
 # entry points returning int64_t (byte counts) instead of an error code / int count
 RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))} | \
     {n for n in SIGNATURES_GPE3D if n.endswith(("_doubles", "_launches"))} | \
@@ -282,7 +296,8 @@ RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))} | \
     {n for n in SIGNATURES_FPE_ERR if n.endswith("_doubles")} | \
     {n for n in SIGNATURES_GPE2D if n.endswith(("_doubles", "_launches"))} | \
     {n for n in SIGNATURES_BAG3D if n.endswith("_floats")} | \
-    {n for n in SIGNATURES_NIOATTN if n.endswith("_floats")}
+    {n for n in SIGNATURES_NIOATTN if n.endswith("_floats")} | \
+    {n for n in SIGNATURES_PHYSATTN if n.endswith("_floats")}
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_int64, "f": ctypes.c_float,
        "d": ctypes.c_double, "s": ctypes.c_void_p}
@@ -310,7 +325,8 @@ def load():
         for name, sig in {**SIGNATURES, **SIGNATURES_CONV3D, **SIGNATURES_FPE, **SIGNATURES_GPE2D,
                           **SIGNATURES_BAG3D, **SIGNATURES_GPE3D, **SIGNATURES_FPE_ERR,
                           **SIGNATURES_GPE3D_ERR, **SIGNATURES_GPE2D_ERR,
-                          **SIGNATURES_NIOATTN, **SIGNATURES_UNET3D}.items():
+                          **SIGNATURES_NIOATTN, **SIGNATURES_UNET3D,
+                          **SIGNATURES_PHYSATTN}.items():
             fn = getattr(lib, name)
             fn.argtypes = [_CT[c] for c in sig]
             fn.restype = ctypes.c_int64 if name in RET64 else ctypes.c_int
@@ -324,7 +340,7 @@ def exported_symbols():
     return (list(SIGNATURES) + list(SIGNATURES_CONV3D) + list(SIGNATURES_FPE) + list(SIGNATURES_GPE2D) +
             list(SIGNATURES_BAG3D) + list(SIGNATURES_GPE3D) + list(SIGNATURES_FPE_ERR) +
             list(SIGNATURES_GPE3D_ERR) + list(SIGNATURES_GPE2D_ERR) + list(SIGNATURES_NIOATTN) +
-            list(SIGNATURES_UNET3D) + ["blindno_error_string"])
+            list(SIGNATURES_UNET3D) + list(SIGNATURES_PHYSATTN) + ["blindno_error_string"])
 
 
 def stream_ptr(device=None):

@@ -10,7 +10,10 @@ encoder kernels and the 1D GPE head layout:
   2d_Non_conservative_FPE   heads fno_Fx, fno_Fy; Encoder2D (3,2)
                             (2d_Non_conservative_FPE/NIOModules.py:13-82,503-577; Baselines.py:200)
   both 2D experiments       NIOFP2D_attn (2d_FPE/NIOModules.py:410-504) with the same heads and
-                            Encoder2D kernels as NIOFP2D (blindno.nio.NIOFP2D_attn)
+                            Encoder2D kernels as NIOFP2D (blindno.nio.NIOFP2D_attn);
+                            NIOFP2D_Trans (2d_FPE/NIOModules.py:85-166): the Transolver snapshot
+                            encoder on csrc/physattn.hip (blindno.nio.NIOFP2D_Trans), heads
+                            fno_drift, fno_diffusion in both, the unused Encoder2D as NIOFP2D's
   1d_FPE                    NIOFP / NIOFP_FNO heads fno_drift, fno_diffusion; Encoder (5,4,15)
                             (1d_FPE/NIOModules.py:15-155; 1d_FPE/Baselines.py:254-287)
   1d_GPE                    NIOFP_schrodinger / NIOFP_FNO head fno_V; Encoder (5,7,4) + conv4
@@ -18,7 +21,7 @@ encoder kernels and the 1D GPE head layout:
 
 The attention UNet ("BlinDNO") maps to blindno.unet: PermInvUNet_attn (2d_FPE),
 its ConvBlock copy PermInvUNet_attn_NC (2d_Non_conservative_FPE), PermInvUNet_attn1D(_bag)
-(1d_FPE) and the one-head 1d_GPE copies.  Classes outside the hot-path scope (Transolver /
+(1d_FPE) and the one-head 1d_GPE copies.  Classes outside the hot-path scope (NIOFP2D_Trans_attn /
 plain-UNet / ODE variants) are importable -- the
 reference scripts import them next to the in-scope ones -- but raise NotImplementedError when
 constructed.  ``FNOModules`` is whole: SpectralConv3d / FNO3d run on the HIP device like the 1D
@@ -108,6 +111,22 @@ class _NIOFP2D_attn_nc(_nio.NIOFP2D_attn):
                          branch_last_kernel=(3, 2))
 
 
+class _NIOFP2D_Trans_2d(_nio.NIOFP2D_Trans):
+    def __init__(self, input_dimensions_trunk, n_hidden_layers, neurons, n_basis, fno_layers,
+                 width, modes, output_dim):
+        super().__init__(input_dimensions_trunk, n_hidden_layers, neurons, n_basis, fno_layers,
+                         width, modes, output_dim, heads=("fno_drift", "fno_diffusion"),
+                         branch_last_kernel=(2, 1))
+
+
+class _NIOFP2D_Trans_nc(_nio.NIOFP2D_Trans):
+    def __init__(self, input_dimensions_trunk, n_hidden_layers, neurons, n_basis, fno_layers,
+                 width, modes, output_dim):
+        super().__init__(input_dimensions_trunk, n_hidden_layers, neurons, n_basis, fno_layers,
+                         width, modes, output_dim, heads=("fno_drift", "fno_diffusion"),
+                         branch_last_kernel=(3, 2))
+
+
 # ------------------------------------------------------------------------------- 1D
 class _NIOFP_FNO_1d(_nio.NIOFP_FNO):
     def __init__(self, fno_layers, width, modes, output_dim, device):
@@ -144,13 +163,13 @@ def _oos(where, *names):
     return {n: _out_of_scope(n, where) for n in names}
 
 
-_2D_OOS = ("NIOFP2D_Trans", "NIOFP2D_Trans_attn", "NIOFP_ode", "PermInvUNet")
+_2D_OOS = ("NIOFP2D_Trans_attn", "NIOFP_ode", "PermInvUNet")
 
 EXPERIMENTS = {
     "2d_FPE": dict(
         NIOModules=dict(NIOFP2D=_NIOFP2D_2d, NIOFP2D_FNO=_NIOFP2D_FNO_2d, NIOFP=_NIOFP_1d,
                         NIOFP2D_FNO_attn=_NIOFP2D_FNO_attn_2d, NIOFP2D_attn=_NIOFP2D_attn_2d,
-                        NIOFP3D=_nio.NIOFP3D,
+                        NIOFP2D_Trans=_NIOFP2D_Trans_2d, NIOFP3D=_nio.NIOFP3D,
                         PermInvUNet_attn=_unet.PermInvUNet_attn, ConvNeXtBlock=_unet.ConvNeXtBlock,
                         TemporalSelfAttention=_unet.TemporalSelfAttention,
                         draw_bag=_nio.draw_bag, **_oos("2d_FPE/NIOModules.py", *_2D_OOS)),
@@ -158,7 +177,7 @@ EXPERIMENTS = {
     "2d_Non_conservative_FPE": dict(
         NIOModules=dict(NIOFP2D=_NIOFP2D_nc, NIOFP2D_FNO=_NIOFP2D_FNO_nc, NIOFP=_NIOFP_1d,
                         NIOFP2D_FNO_attn=_NIOFP2D_FNO_attn_nc, NIOFP2D_attn=_NIOFP2D_attn_nc,
-                        NIOFP3D=_nio.NIOFP3D,
+                        NIOFP2D_Trans=_NIOFP2D_Trans_nc, NIOFP3D=_nio.NIOFP3D,
                         PermInvUNet_attn=_unet.PermInvUNet_attn_NC,
                         TemporalSelfAttention=_unet.TemporalSelfAttention,
                         draw_bag=_nio.draw_bag,

@@ -1,5 +1,6 @@
-"""Snapshot-bag (time-label-free) models: NIOFP2D_FNO, NIOFP_FNO, NIOFP2D, NIOFP2D_attn, NIOFP,
-NIOFP_schrodinger, NIOFP3D -- drop-in for the reference's NIOModules -- and NIOFP3D_FNO, the
+"""Snapshot-bag (time-label-free) models: NIOFP2D_FNO, NIOFP_FNO, NIOFP2D, NIOFP2D_attn,
+NIOFP2D_Trans, NIOFP, NIOFP_schrodinger, NIOFP3D -- drop-in for the reference's NIOModules -- and
+NIOFP3D_FNO, the
 project's own 3D FNO-NIO (the reference has no such class).
 
 Same constructor signatures, attribute names and initialisation order as
@@ -23,6 +24,7 @@ from . import ops
 from .deeponet import FFN, DeepOnetNoBiasOrg
 from .encoders import Encoder, Encoder2D, Encoder3D, Encoder3D_down
 from .fno import FNO1d, FNO2d, FNO3d, fno_params
+from .transolver import Transolver2D
 
 
 def draw_bag(T: int):
@@ -393,6 +395,61 @@ class NIOFP2D_attn(nn.Module):
         h = ops.NIOAttnFn.apply(w, basis, self.deeponet.b0, g, self.fc0.weight.data,
                                 self.fc0.bias.data)
         return _run_heads(self, h.view(B, nx, ny, -1))
+
+
+class NIOFP2D_Trans(nn.Module):
+    """Transolver snapshot encoder + FNO heads, 2d_FPE/NIOModules.py:85-166 and
+    2d_Non_conservative_FPE/NIOModules.py:84-165 (both name the heads fno_drift / fno_diffusion).
+
+    Every drawn snapshot goes through ``trans_input`` = Transolver2D(space_dim=2, n_layers=3,
+    n_hidden=32, n_head=4, mlp_ratio=1, fun_dim=1, out_dim=1, slice_num=16, H=W=61) as the point
+    features [rho, gx, gy] (the reference calls ``trans_input(x_input, grid_r)``, whose forward
+    concatenates ``(x, fx)``); the bag mean with fc0 (read through ``.data``, never trained) and
+    the two FNO heads follow as in NIOFP2D_FNO.  ``branch`` = Encoder2D(n_basis) and the
+    Transolver's ``placeholder`` are built and never used: they are part of the checkpoint layout.
+    Registration order (branch, fc0, trans_input, heads) follows the reference.
+
+    The Transolver has LayerNorm and no BatchNorm, so a snapshot's encoding does not depend on the
+    rest of the bag: it runs once per distinct snapshot of the with-replacement draw, and the bag
+    mean (and its adjoint) weights each by multiplicity / L."""
+
+    GRID = 61      # the reference hard-codes H = W = 61 in the Transolver's reshape
+
+    def __init__(self, input_dimensions_trunk, n_hidden_layers, neurons, n_basis, fno_layers,
+                 width, modes, output_dim, heads: Sequence[str] = ("fno_drift", "fno_diffusion"),
+                 branch_last_kernel=(2, 1)):
+        super().__init__()
+        output_dimensions = n_basis
+        self.fno_layers = fno_layers
+        self.branch = Encoder2D(output_dimensions, last_kernel=branch_last_kernel)
+        self.fc0 = nn.Linear(3, width)
+        self.trans_input = Transolver2D(space_dim=2, n_layers=3, n_hidden=32, dropout=0.0, n_head=4,
+                                        Time_Input=False, mlp_ratio=1, fun_dim=1, out_dim=1,
+                                        slice_num=16, ref=8, unified_pos=False, H=self.GRID,
+                                        W=self.GRID)
+        self._heads = tuple(heads)
+        for name in self._heads:
+            setattr(self, name, FNO2d(modes=modes, width=width, n_layers=self.fno_layers,
+                                      input_dim=width, output_dim=1))
+
+    # parameters that never receive a gradient (the reference's Adam leaves them unchanged)
+    unused_prefixes = ("branch.", "trans_input.placeholder", "fc0.")
+
+    def forward(self, x, grid, bag_idx=None):
+        """x (B, T, 61, 61), grid (61, 61, 2) -> (B, 61, 61, 2).  ``bag_idx`` overrides the
+        train-mode draw (draw_bag: with replacement); eval mode uses all T snapshots."""
+        ops.require_device(x, grid)
+        n = self.GRID
+        if x.dim() != 4 or tuple(x.shape[2:]) != (n, n) or tuple(grid.shape) != (n, n, 2):
+            raise ValueError(f"NIOFP2D_Trans: the reference's Transolver is built for a {n} x {n} grid; "
+                             f"got x {tuple(x.shape)} and grid {tuple(grid.shape)}")
+        x, L, lw = _select(self, x, bag_idx, dedup=True)
+        B = x.shape[0]
+        g = grid.permute(2, 0, 1).unsqueeze(0).expand(B * L, 2, n, n)
+        inp = torch.cat((x.reshape(B * L, 1, n, n), g), dim=1)        # [rho, gx, gy] planes
+        u = self.trans_input.forward_planes(inp)                      # (B L, 1, n, n)
+        h = _bag_mean_2d(self, u, grid, B, L, n, n, lw)
+        return _run_heads(self, h)
 
 
 class NIOFP3D(nn.Module):

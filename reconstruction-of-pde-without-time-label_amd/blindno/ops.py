@@ -2691,3 +2691,107 @@ class BNActFn(torch.autograd.Function):
         call("blindno_bn_act_bwd", ptr(dy), ptr(z), ptr(gamma), ptr(save), ptr(dz), ptr(dgamma), ptr(dbeta),
              ptr(partial), ptr(coef), n, Npad, C, HW, slope, use_batch, stream_ptr())
         return dz, dgamma, dbeta, None, None, None
+
+
+# ---------------------------------------------------------------------------- Transolver
+
+
+def physattn_ok(S, H, W, heads, D, G) -> bool:
+    """The physics-attention kernels take this configuration (blindno_physattn_ok)."""
+    return bool(query("blindno_physattn_ok", int(S), int(H), int(W), int(heads), int(D), int(G)))
+
+
+class PhysAttnFn(torch.autograd.Function):
+    """Physics attention of the structured-mesh Transolver after its two 3x3 convolutions
+    (model/Physics_Attention.py:98-116; csrc/physattn.hip, include/blindno_physattn.h): xf
+    (S, 64, H, W) channel planes, channels 0..31 = in_project_x(x), 32..63 = in_project_fx(x)
+    -> to_out(deslice(attention(slice))) (+ res) as (S, 32, H, W) planes.  4 heads, D = 8, G = 16
+    only (ValueError otherwise).  The slice weights are stored once, as (S, 4, 16, H W) planes,
+    and read by the deslice and both backward passes; ox is never stored."""
+
+    @staticmethod
+    def forward(ctx, xf, temperature, Ws, bs, Wq, Wk, Wv, Wo, bo, res=None):
+        require_device(xf, temperature, Ws, bs, Wq, Wk, Wv, Wo, bo, res)
+        if xf.dim() != 4:
+            raise ValueError(f"PhysAttnFn: xf must be (S, 64, H, W), got {tuple(xf.shape)}")
+        S, C2, H, W = xf.shape
+        heads = temperature.numel()
+        G, D = tuple(Ws.shape) if Ws.dim() == 2 else (0, 0)
+        if not physattn_ok(S, H, W, heads, D, G) or C2 != 2 * heads * D:
+            raise ValueError(f"PhysAttnFn: only heads = 4, dim_head = 8, slice_num = 16 (the "
+                             f"reference's Transolver) run on the HIP kernels; got heads = {heads}, "
+                             f"dim_head = {D}, slice_num = {G}, xf {tuple(xf.shape)}")
+        C, N = heads * D, H * W
+        if (tuple(bs.shape) != (G,) or tuple(Wq.shape) != (D, D) or tuple(Wk.shape) != (D, D) or
+                tuple(Wv.shape) != (D, D) or tuple(Wo.shape) != (C, C) or tuple(bo.shape) != (C,) or
+                (res is not None and tuple(res.shape) != (S, C, H, W))):
+            raise ValueError("PhysAttnFn: parameter shapes do not match heads = 4, D = 8, G = 16")
+        xf = _c(xf)
+        prm = [_c(t) for t in (temperature.reshape(-1), Ws, bs, Wq, Wk, Wv, Wo, bo)]
+        res = _c(res) if res is not None else None
+        w = _empty(S, heads, G, N, like=xf)
+        tok = _empty(S, heads, G, D, like=xf)
+        norm = _empty(S, heads, G, like=xf)
+        A = _empty(S, heads, G, G, like=xf)
+        otok = _empty(S, heads, G, D, like=xf)
+        scratch = _empty(query("blindno_physattn_fwd_scratch_floats", S, H, W), like=xf)
+        y = _empty(S, C, H, W, like=xf)
+        fm = xf[:, C:]
+        call("blindno_physattn_fwd", ptr(xf), ptr(fm), 2 * C * N, *[ptr(t) for t in prm], ptr(res),
+             ptr(w), ptr(tok), ptr(norm), ptr(A), ptr(otok), ptr(scratch), ptr(y), S, H, W,
+             stream_ptr())
+        ctx.save_for_backward(xf, *prm[:7], w, tok, norm, A, otok)
+        ctx.tshape = tuple(temperature.shape)
+        ctx.has_res = res is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xf, temperature, Ws, bs, Wq, Wk, Wv, Wo, w, tok, norm, A, otok = ctx.saved_tensors
+        S, C2, H, W = xf.shape
+        C, N = C2 // 2, H * W
+        dy = _c(dy)
+        scratch = _empty(query("blindno_physattn_bwd_scratch_floats", S, H, W), like=dy)
+        dxf = torch.empty_like(xf)
+        dT, dWs, dbs = torch.empty_like(temperature), torch.empty_like(Ws), torch.empty_like(bs)
+        dWq, dWk, dWv = torch.empty_like(Wq), torch.empty_like(Wk), torch.empty_like(Wv)
+        dWo, dbo = torch.empty_like(Wo), _empty(C, like=dy)
+        call("blindno_physattn_bwd", ptr(dy), ptr(xf), ptr(xf[:, C:]), 2 * C * N, ptr(temperature),
+             ptr(Ws), ptr(bs), ptr(Wq), ptr(Wk), ptr(Wv), ptr(Wo), ptr(w), ptr(tok), ptr(norm), ptr(A),
+             ptr(otok), ptr(scratch), ptr(dxf), ptr(dxf[:, C:]), 2 * C * N, ptr(dT), ptr(dWs), ptr(dbs),
+             ptr(dWq), ptr(dWk), ptr(dWv), ptr(dWo), ptr(dbo), S, H, W, stream_ptr())
+        return (dxf, dT.reshape(ctx.tshape), dWs, dbs, dWq, dWk, dWv, dWo, dbo,
+                dy if ctx.has_res else None)
+
+
+class LayerNormPlanesFn(torch.autograd.Function):
+    """nn.LayerNorm(32) over the channel planes of x (S, 32, H, W) (csrc/physattn.hip): a thread
+    per point, dgamma / dbeta through fixed-order partials."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        require_device(x, gamma, beta)
+        if x.dim() < 3 or x.shape[1] != 32 or gamma.numel() != 32 or beta.numel() != 32:
+            raise ValueError(f"LayerNormPlanesFn: 32 channel planes only, got x {tuple(x.shape)}")
+        x, gamma, beta = _c(x), _c(gamma), _c(beta)
+        S, C = x.shape[:2]
+        HW = x[0, 0].numel()
+        y = torch.empty_like(x)
+        mean, rstd = _empty(S, HW, like=x), _empty(S, HW, like=x)
+        call("blindno_ln_planes_fwd", ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd),
+             S, C, HW, float(eps), stream_ptr())
+        ctx.save_for_backward(x, gamma, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, mean, rstd = ctx.saved_tensors
+        S, C = x.shape[:2]
+        HW = x[0, 0].numel()
+        dy = _c(dy)
+        dx = torch.empty_like(x)
+        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(gamma)
+        partial = _empty(S * query("blindno_ln_planes_nblk", HW) * 2 * C, like=dy)
+        call("blindno_ln_planes_bwd", ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx),
+             ptr(dgamma), ptr(dbeta), ptr(partial), S, C, HW, stream_ptr())
+        return dx, dgamma, dbeta, None

@@ -168,11 +168,23 @@ def _own_experiments(model: str = "fno"):
     ``_experiments`` (the reference's train_*.py tables, with the NIO-FNO 2d_GPE / 3d_FPE entries)
     does not hold.  ``model="unet"``: 3d_FPE with PermInvUNet_attn3D(1, 2, 1, 3, (n, n, n)) on
     datagen.fpe_3d_dataset files -- the 2D UNet entry's lr, batch and eval period, an eager step,
-    one process only, results_3d_FPE_unet/."""
+    one process only, results_3d_FPE_unet/.  ``model="trans"``: 2d_FPE with NIOFP2D_Trans(2, 3, 100,
+    25, 3, 12, 32, 2) (2d_FPE/NIOModules.py:85-166; 61 x 61 datasets only) -- the 2d_FPE UNet entry's
+    lr, batch and eval period, an eager step, one process only, results_2d_FPE_trans/."""
+    all4 = ("train_losses", "test_losses", "test_losses_drift", "test_losses_diffusion")
+    if model == "trans":
+        from . import data, nio
+        from .encoders import Encoder2D
+        return {
+            "2d_FPE": Experiment("2d_FPE", 2, data.TrajectoryDataset2D,
+                                 lambda n, dev: nio.NIOFP2D_Trans(
+                                     2, 3, 100, 25, 3, 12, 32, 2,
+                                     branch_last_kernel=Encoder2D.kernel_for_grid(n)),
+                                 5e-4, 4, 5, "results_2d_FPE_trans", True, all4, eager=True),
+        }
     if model != "unet":
         return {}
     from . import data, unet3d
-    all4 = ("train_losses", "test_losses", "test_losses_drift", "test_losses_diffusion")
     return {
         "3d_FPE": Experiment("3d_FPE", 3, data.TrajectoryDataset3D,
                              lambda n, dev: unet3d.PermInvUNet_attn3D(1, 2, 1, 3, (n, n, n), device=dev),
@@ -364,9 +376,9 @@ class Trainer:
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--experiment", choices=sorted(_experiments()), default="2d_FPE")
-    ap.add_argument("--model", choices=["fno", "unet", "nio"], default="fno",
+    ap.add_argument("--model", choices=["fno", "unet", "nio", "trans"], default="fno",
                     help="fno: train_fno*.py (NIO-FNO); unet: train_unet*.py (attention UNet); "
-                         "nio: train_nio*.py (DeepONet-branch NIO)")
+                         "nio: train_nio*.py (DeepONet-branch NIO); trans: NIOFP2D_Trans (2d_FPE)")
     ap.add_argument("--data", required=True, help="the experiment's dataset file (npz, or the GPE .npy dict)")
     ap.add_argument("--outdir", default=None, help="result directory (default: the reference's)")
     ap.add_argument("--epochs", type=int, default=400)
@@ -381,7 +393,7 @@ def main(argv=None):
     exps = experiments_for(a.model)
     if a.experiment not in exps:
         ap.error(f"--experiment {a.experiment} has no --model {a.model} configuration "
-                 f"(it has: {', '.join(m for m in ('fno', 'unet', 'nio') if a.experiment in experiments_for(m))})")
+                 f"(it has: {', '.join(m for m in ('fno', 'unet', 'nio', 'trans') if a.experiment in experiments_for(m))})")
     exp = exps[a.experiment]
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))

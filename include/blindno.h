@@ -363,6 +363,42 @@ int blindno_rowidft_bwd_lift_zc(const float* Y, const float* dz, const float* X,
                                 const float* wc, const float* tb, const float* tab, float* partial,
                                 int B, int T, int L, int N1, int N2, int C, int P1, int P2, int m1,
                                 int m2, blindno_stream_t stream);
+/* The encoder's first-layer gradients without the row inverse of dz0 (the lifted input is linear
+ * in the one snapshot channel, so they are reductions of spectra and of 16 moments).
+ * blindno_rowidft_bwd_zc_m / _zc_bag_m: blindno_rowidft_bwd_zc / _zc_bag (weight-gradient and
+ * column-DFT partials required) whose partial rows (nchunk, C C + C + 4 C) also carry the moments
+ * M[o][j] = sum over the N1 x N2 crop of dx[o] in_j, in = (u, gx, gy, 1), u = X[b][idx[l]]
+ * (Bn = B L), at columns C C + C + 4 o + j; dx NULL: the field is not stored.  N2 % 4 == 0.
+ * blindno_colmix_u: blindno_colmix that also saves the snapshots' own spectrum U (Bn, m2, K1)
+ * complex (lift only; NULL: none).
+ * blindno_liftgrad_spec: from the first layer's adjoint spectrum G (Bn, m2, C, K1) (colmix dir 1's
+ * Xsave), U, the packed weights Wt, Dg2, fc0 (w0, b0), the layer's 1x1 conv wc and the moments'
+ * partial rows pw (nrow_m, npw; M at column mcol), partials of dWt in ns sample slices, dWp (ns,
+ * m2 K1 C C) complex, and pl (blindno_liftgrad_rows(C, m2, ns, nrow_m), 36) = [dWc (C C) | dbc (C)
+ * | dfc0.weight (C 3) | dfc0.bias (C)]; blindno_reduce_partials finishes both.  Hosts up to two
+ * spectral weight gradients like blindno_rowidft_bwd_lift_zc_mix.  C = 4, m1 = 12. */
+int blindno_rowidft_bwd_zc_m(const float* Y, const float* dz, const float* wc, const float* xsrc,
+                             float* dx, const float* tb, const float* tab, float* part,
+                             const float* Tp, float* partial, const float* X, const int* idx,
+                             const float* grid, int B, int T, int L, int N1, int N2, int C, int P1,
+                             int P2, int m1, int m2, int act, int dN1, int dN2,
+                             blindno_stream_t stream);
+int blindno_rowidft_bwd_zc_bag_m(const float* Y, const float* v, const float* ghat, const float* lw,
+                                 const float* wc, const float* xsrc, float* dx, const float* tb,
+                                 const float* tab, float* part, const float* Tp, float* partial,
+                                 const float* X, const int* idx, const float* grid, int B, int T,
+                                 int L, int N1, int N2, int C, int P1, int P2, int m1, int m2, int act,
+                                 int Ho, int Wo, blindno_stream_t stream);
+int blindno_colmix_u(const float* part, int nbv, const float* Wt, float* Xsave, float* Y, int Bn,
+                     int C, int Cp, int P1, int P2, int m1, int m2, int dir, const float* w0,
+                     const float* b0, const float* Dg2, float* Usave, blindno_stream_t stream);
+int blindno_liftgrad_rows(int C, int m2, int ns, int nrow_m);
+int blindno_liftgrad_spec(const float* G, const float* U, const float* Wt, const float* Dg2,
+                          const float* w0, const float* b0, const float* wc, const float* pw,
+                          int nrow_m, int npw, int mcol, float* dWp, float* pl, int Bn, int C, int P1,
+                          int P2, int m1, int m2, int ns, const void* const* mX,
+                          const void* const* mG, void* const* mOut, const int* mshp, int nmj,
+                          blindno_stream_t stream);
 
 /* 1x1-conv weight/bias gradient partials (for C > 8): partial[nchunk][C*C + C] with
  * dWc[o,i] = sum dz[n,o,.] f(x[n,i,.]),  dbc[o] = sum dz[n,o,.];

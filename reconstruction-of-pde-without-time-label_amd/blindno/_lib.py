@@ -44,6 +44,11 @@ SIGNATURES = {
     "blindno_rowidft_bwd_lift_zc_mix": "ppppppppppp" + "iiiiiiiiii" + "ppppi" + "s",
     "blindno_rowdft_cd_bag": "pppi" + "ppp" + "iiiiiii" + "s",
     "blindno_rowidft_bwd_zc_bag": "pppp" + "i" + "pppppppp" + "iiiiiiiii" + "s",
+    "blindno_rowidft_bwd_zc_m": "p" * 13 + "i" * 13 + "s",
+    "blindno_rowidft_bwd_zc_bag_m": "p" * 15 + "i" * 13 + "s",
+    "blindno_colmix_u": "pippp" + "iiiiiiii" + "pppp" + "s",
+    "blindno_liftgrad_rows": "iiii",
+    "blindno_liftgrad_spec": "pppppppp" + "iii" + "pp" + "iiiiiii" + "pppp" + "i" + "s",
     "blindno_mix_wgrad": "ppppiiiiiis",
     "blindno_mix_wgrad_part": "pppiiiiiiis",
     "blindno_mix_wgrad_multi": "ppppis",

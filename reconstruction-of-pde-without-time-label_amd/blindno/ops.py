@@ -63,6 +63,12 @@ HOST_ENC_MIX = True
 # the bag encoder's spectral-weight pack (with the heads' pack_ahead requests) hosted by its
 # first row-DFT launch (False: a pack launch of its own)
 HOST_PACK = True
+# the bag encoder's first-layer gradients (fc0, the layer's 1x1 conv and spectral weights) from
+# the adjoint spectrum, the snapshots' saved spectrum and 16 moments that the second layer's
+# adjoint sums in its epilogue (blindno_liftgrad_spec): no row inverse of dz0, and dz0 itself is
+# never written (False: blindno_rowidft_bwd_lift_zc_mix on the stored field).  Two-layer
+# encoders on the folded column pass only; read in the forward, which saves the spectrum.
+LIFTGRAD_SPEC = True
 
 
 def set_mix_precision(name: str) -> None:
@@ -1828,11 +1834,17 @@ class _ColSpec:
     def part(self, Cp, like):
         return _empty(self.Bn * self.nb * query("blindno_colspec_nchunk", Cp, self.m2) * 128, like=like)
 
-    def mix(self, part, nbv, Wt, direction, Cp=None, lift=None):
-        """(Xsave, Y) of the summed partials: direction 0 (X, Y = mix) or 1 (G, conj mix)."""
+    def mix(self, part, nbv, Wt, direction, Cp=None, lift=None, usave=None):
+        """(Xsave, Y) of the summed partials: direction 0 (X, Y = mix) or 1 (G, conj mix).
+        ``usave`` (lift): filled with the snapshots' own spectrum U (Bn, m2, K1, 2)."""
         Xs = _empty(self.Bn, self.m2, self.C, self.K1, 2, like=part)
         Y = _empty(self.Bn, self.m2, self.C, self.K1, 2, like=part)
         w0, b0, Dg2 = lift if lift is not None else (None, None, None)
+        if usave is not None:
+            call("blindno_colmix_u", ptr(part), nbv, ptr(Wt), ptr(Xs), ptr(Y), self.Bn, self.C,
+                 Cp or self.C, self.P1, self.P2, self.m1, self.m2, direction, ptr(w0), ptr(b0),
+                 ptr(Dg2), ptr(usave), stream_ptr())
+            return Xs, Y
         call("blindno_colmix", ptr(part), nbv, ptr(Wt), ptr(Xs), ptr(Y), self.Bn, self.C,
              Cp or self.C, self.P1, self.P2, self.m1, self.m2, direction, ptr(w0), ptr(b0), ptr(Dg2),
              stream_ptr())
@@ -1914,6 +1926,10 @@ class BagEncoderFn(torch.autograd.Function):
         cs = _ColSpec(Bn, C, P1, P2, meta.m1, meta.m2, X.device) \
             if colspec_ok(Bn, C, P1, P2, meta.m1, meta.m2) else None
         ctx.cs = cs
+        # the first layer's gradients from spectra (LIFTGRAD_SPEC): the forward keeps the
+        # snapshots' spectrum U0 and the grid planes' Dg2 (fresh / cached buffers, on ctx like bag)
+        ctx.lg = None
+        U0 = None
         Wts_all = pack_w2d_many([(prm[2 + 4 * k], prm[3 + 4 * k]) for k in range(n)], P1,
                                 defer=HOST_PACK and cs is not None)
         if cs is not None:
@@ -1923,6 +1939,10 @@ class BagEncoderFn(torch.autograd.Function):
             try:
                 Dg2 = _grid_spec2(grid, N1, N2, P1, P2, meta.m1, meta.m2)
                 part = cs.part(1, X)
+                # (only when a backward will follow: needs_input_grad is all False under no_grad)
+                if LIFTGRAD_SPEC and n == 2 and any(ctx.needs_input_grad):
+                    U0 = _empty(Bn, meta.m2, cs.K1, 2, like=X)
+                    ctx.lg = (U0, Dg2)
             finally:            # never leave the held-back pack behind (its Wts die with us)
                 pk = take_deferred_pack()
             if pk is not None:      # the pack rides along the first row DFT (colmix reads it)
@@ -1938,7 +1958,8 @@ class BagEncoderFn(torch.autograd.Function):
                 Wt = Wts_all[k]
                 last = k == n - 1
                 Xk, Y = cs.mix(part, nbv, Wt, 0, Cp=1 if k == 0 else C,
-                               lift=(fc0w, fc0b, Dg2) if k == 0 else None)
+                               lift=(fc0w, fc0b, Dg2) if k == 0 else None,
+                               usave=U0 if k == 0 else None)
                 z = _empty(Bn, C, P1, P2, like=X)
                 part = None if last else cs.part(C, X)
                 if k == 0:
@@ -2059,6 +2080,8 @@ class BagEncoderFn(torch.autograd.Function):
         crop = (Ho, Wo) if n >= 2 else None
         cs = ctx.cs
         ctx.cs = None
+        lg = ctx.lg
+        ctx.lg = None
         # the folded column pass with the bag-level projection: dz = lw_l ghat v is formed on load
         # by its two readers (the last layer's row DFT and row-inverse adjoint), so the projection
         # backward neither writes dz nor reads v (a field write and read less per step)
@@ -2100,17 +2123,66 @@ class BagEncoderFn(torch.autograd.Function):
                 call("blindno_rowdft_cd", ptr(dz), ptr(part), ptr(cs.Tp), ptr(cs.tab), Bn, C, P1, P2, meta.m2,
                      0, valid[0], valid[1], stream_ptr())
             nbv = (valid[0] + 15) // 16
-            # the spectral weight gradients of both layers ride along the first layer's adjoint
-            # launch (blindno_rowidft_bwd_lift_zc_mix) under deferred_reductions()
+            # under deferred_reductions() the spectral weight gradients ride along the last launch
+            # of this backward: with LIFTGRAD_SPEC the second layer's is hosted by
+            # blindno_liftgrad_spec, which forms the first layer's itself; otherwise both layers'
+            # are hosted by the first layer's adjoint (blindno_rowidft_bwd_lift_zc_mix)
             hosted = [] if (_DEFER is not None and HOST_ENC_MIX and n <= 2) else None
             for k in reversed(range(n)):
                 off = 2 + 4 * k
                 w1, w2, cw, cb = prm[off:off + 4]
                 G, Yb = cs.mix(part, nbv, Wts[k], 1)
+                if k == 0 and lg is not None:
+                    # (the mixed Yb is not read here: only G and the sums over it are)
+                    nel = meta.m2 * sh.K1 * C * C * 2
+                    ns = query("blindno_mix_wgrad_nsplit", Bn, C, C, sh.K1, meta.m2)
+                    dWp = _empty(ns, nel, like=gh)
+                    npl = C * C + C + 4 * C
+                    rows = query("blindno_liftgrad_rows", C, meta.m2, ns, nchunk)
+                    pl = _empty(rows, npl, like=gh)
+                    jobs = hosted or []
+                    nj = len(jobs)
+                    call("blindno_liftgrad_spec", ptr(G), ptr(lg[0]), ptr(Wts[0]), ptr(lg[1]), ptr(fc0w),
+                         ptr(fc0b), ptr(cw), ptr(pw), nchunk, npl, C * C + C, ptr(dWp), ptr(pl), Bn, C,
+                         P1, P2, meta.m1, meta.m2, ns,
+                         (ctypes.c_void_p * max(1, nj))(*[j[0].data_ptr() for j in jobs]),
+                         (ctypes.c_void_p * max(1, nj))(*[j[1].data_ptr() for j in jobs]),
+                         (ctypes.c_void_p * max(1, nj))(*[j[2].data_ptr() for j in jobs]),
+                         (ctypes.c_int * max(7, 7 * nj))(*[v for j in jobs for v in j[3]]), nj,
+                         stream_ptr())
+                    dWt = reduce_partials(dWp, ns, nel).view(meta.m2, sh.K1, C, C, 2)
+                    grads[off], grads[off + 1] = unpack_weights(dWt, (w1, w2), P1, 2)
+                    g = reduce_partials(pl, rows, npl)
+                    grads[off + 2] = g[:C * C].view_as(cw)
+                    grads[off + 3] = g[C * C:C * C + C]
+                    grads[0] = g[C * C + C:C * C + 4 * C].view(C, 3)
+                    grads[1] = g[C * C + 4 * C:]
+                    break
                 dWt = k_mix_wgrad(Xs[k], G, Bn, C, C, sh.K1, meta.m2, deferrable=True, jobs=hosted)
                 grads[off], grads[off + 1] = unpack_weights(dWt, (w1, w2), P1, 2)
                 dv = crop if (k == n - 1 and crop) else (P1, P2)
-                if k > 0:
+                if k > 0 and lg is not None:
+                    # the first layer's gradients need only dz0's column-DFT partials and its
+                    # moments against (u, gx, gy, 1): the field itself is not stored
+                    nchunk = query("blindno_colspec_bwd_nchunk", Bn, P1)
+                    npw = C * C + C + 4 * C
+                    pw = _empty(nchunk, npw, like=gh)
+                    part = cs.part(C, gh)
+                    if bagdz:
+                        call("blindno_rowidft_bwd_zc_bag_m", ptr(Yb), ptr(bag[1]), ptr(sgr), ptr(lw), ptr(cw),
+                             ptr(zs[k - 1]), None, ptr(cs.tb), ptr(cs.tab), ptr(part), ptr(cs.Tp), ptr(pw),
+                             ptr(X), ptr(idx_t), ptr(grid), B, T, L, N1, N2, C, P1, P2, meta.m1, meta.m2, 1,
+                             Ho, Wo, stream_ptr())
+                    else:
+                        call("blindno_rowidft_bwd_zc_m", ptr(Yb), ptr(dz), ptr(cw), ptr(zs[k - 1]), None,
+                             ptr(cs.tb), ptr(cs.tab), ptr(part), ptr(cs.Tp), ptr(pw), ptr(X), ptr(idx_t),
+                             ptr(grid), B, T, L, N1, N2, C, P1, P2, meta.m1, meta.m2, 1, dv[0], dv[1],
+                             stream_ptr())
+                    g = reduce_partials(pw, nchunk, npw)
+                    grads[off + 2], grads[off + 3] = g[:C * C].view_as(cw), g[C * C:C * C + C]
+                    dz = None
+                    nbv = P1 // 16
+                elif k > 0:
                     nchunk = query("blindno_colspec_bwd_nchunk", Bn, P1)
                     pw = _empty(nchunk, C * C + C, like=gh)
                     dx = _empty(Bn, C, P1, P2, like=gh)

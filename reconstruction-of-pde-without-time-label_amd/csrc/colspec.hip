@@ -156,7 +156,8 @@ __global__ __launch_bounds__(64 * kCdWaves) void rowdft_cd_pack_kernel(
 // beside them.  LIFT (DIR 0): the partials are the snapshot's (one channel, U), and
 // Xs[k][c] = W0[c,0] U[k] + W0[c,1] Dg2[k][0] + W0[c,2] Dg2[k][1] + b0[c] Dg2[k][2] (the lifted
 // field's spectrum, by linearity; Dg2 the grid / bias planes' spectrum).  Wt == NULL: Xsave
-// only (no mix; the Dg2 precompute).
+// only (no mix; the Dg2 precompute).  Usave (LIFT): the snapshot's own spectrum U (n, m2, K1)
+// (the first layer's gradients are reductions against it: liftgrad_kernel).
 constexpr int kMixThreads = 256;
 constexpr int kMixJ = 8;                           // kept rows per workgroup (one M tile's j)
 constexpr int kMixMaxB = 20;                       // blocks per sample (P1 <= 320)
@@ -164,7 +165,7 @@ template <int DIR, bool LIFT>
 __global__ __launch_bounds__(kMixThreads) void colmix_kernel(
     const float* __restrict__ part, int nbv, const float2* __restrict__ Wt, float2* __restrict__ Xsave,
     float2* __restrict__ Y, int C, int Cp, int P1, int P2, int m2, const float* __restrict__ w0,
-    const float* __restrict__ b0, const float2* __restrict__ Dg2) {
+    const float* __restrict__ b0, const float2* __restrict__ Dg2, float2* __restrict__ Usave) {
   extern __shared__ float2 smx[];
   float2* sP = smx;                                // [m2][Cp][kMixJ]: the summed partials
   float2* sX = sP + m2 * Cp * kMixJ;               // [m2][C][kMixJ]: Xs (LIFT), else sP
@@ -227,6 +228,7 @@ __global__ __launch_bounds__(kMixThreads) void colmix_kernel(
       v.x = fmaf(a, u.x, fmaf(bx, d0.x, fmaf(by, d1.x, bb * d2.x)));
       v.y = fmaf(a, u.y, fmaf(bx, d0.y, fmaf(by, d1.y, bb * d2.y)));
       Xs[e] = v;
+      if (Usave && c == 0) Usave[((int64_t)n * m2 + k) * kCsK1 + j0 + jl] = u;
     } else {
       v = Xs[e];
       if (DIR == 1) {
@@ -401,10 +403,13 @@ BLINDNO_API int blindno_rowdft_bag_lift_cd_pack(const float* X, const int* idx, 
 // Y (Bn, m2, C, K1) complex; Wt (m2, K1, C, C) complex (blindno_pack_w2d) or NULL (Xsave only).
 // dir 0 forward, 1 adjoint.  w0 / b0 / Dg2 (LIFT, dir 0, Cp = 1): fc0's weight (C, 3), bias (C)
 // and the grid planes' spectrum Dg2 (m2, 3, K1) complex.
-BLINDNO_API int blindno_colmix(const float* part, int nbv, const float* Wt, float* Xsave, float* Y,
-                               int Bn, int C, int Cp, int P1, int P2, int m1, int m2, int dir,
-                               const float* w0, const float* b0, const float* Dg2, void* stream) {
+// Usave (lift only, or NULL): the snapshots' own spectrum U (Bn, m2, K1) complex.
+BLINDNO_API int blindno_colmix_u(const float* part, int nbv, const float* Wt, float* Xsave, float* Y,
+                                 int Bn, int C, int Cp, int P1, int P2, int m1, int m2, int dir,
+                                 const float* w0, const float* b0, const float* Dg2, float* Usave,
+                                 void* stream) {
   const bool lift = w0 != nullptr;
+  if (Usave && !lift) return (int)hipErrorInvalidValue;
   if (!part || Bn <= 0 || C <= 0 || C > 16 || m2 <= 0 || m2 > 16 || m1 != 12 ||
       kept_rows_count(m1, P1) != kCsK1 || P1 % 16 || nbv < 1 || nbv > P1 / 16 ||
       (Wt && !Y) || (!Wt && !Xsave) || (lift && (Cp != 1 || !b0 || !Dg2 || dir != 0)) ||
@@ -416,10 +421,229 @@ BLINDNO_API int blindno_colmix(const float* part, int nbv, const float* Wt, floa
   const float2* W = (const float2*)Wt;
 #define CM(D_, L_)                                                                             \
   colmix_kernel<D_, L_><<<Bn * kCsMT2, kMixThreads, sh, st>>>(                                 \
-      part, nbv, W, (float2*)Xsave, (float2*)Y, C, Cp, P1, P2, m2, w0, b0, (const float2*)Dg2)
+      part, nbv, W, (float2*)Xsave, (float2*)Y, C, Cp, P1, P2, m2, w0, b0, (const float2*)Dg2,   \
+      (float2*)Usave)
   if (lift) CM(0, true);
   else if (dir == 0) CM(0, false);
   else CM(1, false);
 #undef CM
+  return (int)hipGetLastError();
+}
+
+BLINDNO_API int blindno_colmix(const float* part, int nbv, const float* Wt, float* Xsave, float* Y,
+                               int Bn, int C, int Cp, int P1, int P2, int m1, int m2, int dir,
+                               const float* w0, const float* b0, const float* Dg2, void* stream) {
+  return blindno_colmix_u(part, nbv, Wt, Xsave, Y, Bn, C, Cp, P1, P2, m1, m2, dir, w0, b0, Dg2,
+                          nullptr, stream);
+}
+
+// ------------------------------------------------- first-layer gradients from spectra and moments
+// The encoder's first layer z0 = S0(x0) + Wc0 x0 + bc0 reads x0 = pad(fc0(u, gx, gy)), which is
+// linear in the one snapshot channel u: x0[c] = sum_j A[c][j] in_j, in = (u, gx, gy, 1 on the
+// crop), A = [fc0.weight | fc0.bias].  With the adjoint spectrum G (n, m2, C, K1) of dz0 (colmix
+// DIR 1's Xsave), the snapshots' spectrum U (n, m2, K1), the grid planes' Dg2 (m2, 3, K1) and
+//   Ru[o] = sum_n conj(U[n]) G[n][o],   R1[o] = sum_n G[n][o]            (per mode (k, j))
+// every gradient of the layer follows without the row inverse of dz0 (Parseval):
+//   dWt[k][j][c][o] = A[c][0] Ru[o] + conj(Gam_c) R1[o],   Gam_c = A[c][1] Dg2[0] + A[c][2] Dg2[1]
+//                                                                  + A[c][3] Dg2[2]
+//     (= sum_n conj(Xs[n][c]) G[n][o], mix_wgrad_block's product, as Xs[n][c] = A[c][0] U[n] + Gam_c)
+//   dA[c][0]  = sum_o Wc0[o][c] M[o][0] + sum_{k,j,o} Re(conj(Ru[o]) Wt[k][j][c][o])
+//   dA[c][jj] = sum_o Wc0[o][c] M[o][jj] + sum_{k,j,o} Re(Dg2[jj - 1] conj(R1[o]) Wt[k][j][c][o])
+//   dWc0[o][c] = sum_j A[c][j] M[o][j],   dbc0[o] = P1 P2 Re R1[o] at the DC mode
+// with the moments M[o][j] = sum over the crop of dz0[o] in_j (rowfuse_kernel MG's partial
+// columns).  All of it is linear in the sums over the samples and in M, so the kernel emits
+// PARTIALS that the fixed-order reduction finishes: sample slice y of ns forms Ru, R1 over its
+// samples (fp64 accumulation, as mix_wgrad_block) and writes dWp[y] (m2 K1 C C complex) plus one
+// row per workgroup of the small gradients; each partial row of M is mapped through the same
+// linear forms into one more row.  Row layout (36): dWc0 [o][c], dbc0 [o], dfc0W [c][3], dfc0b [c].
+struct LiftGradArgs {
+  const float2* G;
+  const float2* U;
+  const float2* Wt;
+  const float2* Dg2;
+  const float* w0;
+  const float* b0;
+  const float* wc;
+  const float* pw;            // the moments' partial rows (nrow_m, npw), M at column mcol + 4 o + j
+  float2* dWp;                // (ns, m2 K1 C C)
+  float* pl;                  // (gx ns + nrow_m, 36)
+  int Bn, m2, ns, gx, nrow_m, npw, mcol, nspec, nmrow;
+  float p1p2;
+  int nmj;
+  int mcum[3];
+  MixWgradJob mj[2];
+};
+constexpr int kLgC = 4;
+constexpr int kLgRow = kLgC * kLgC + kLgC + 4 * kLgC;
+
+__global__ __launch_bounds__(kBlock) void liftgrad_kernel(LiftGradArgs a) {
+  constexpr int C = kLgC;
+  const int b = blockIdx.x;
+  if (b >= a.nspec + a.nmrow) {                   // hosted spectral weight gradients
+    int r = b - a.nspec - a.nmrow;
+    const int q = (a.nmj > 1 && r >= a.mcum[1]) ? 1 : 0;
+    r -= a.mcum[q];
+    const MixWgradJob& mj = a.mj[q];
+    mix_wgrad_block(mj.X, mj.Gs, mj.out, mj.Bn, mj.Ci, mj.Co, mj.K1, mj.m2, r % mj.gx,
+                    (r / mj.gx) % mj.gy, r / (mj.gx * mj.gy), mj.gx, mj.gy, mj.gz);
+    return;
+  }
+  if (b >= a.nspec) {                             // the moments' rows through the linear forms
+    const int e = (b - a.nspec) * kBlock + threadIdx.x;
+    if (e >= a.nrow_m * kLgRow) return;
+    const int row = e / kLgRow, col = e - row * kLgRow;
+    const float* M = a.pw + (int64_t)row * a.npw + a.mcol;
+    float v;
+    if (col < C * C) {
+      const int o = col / C, c = col - o * C;
+      v = fmaf(a.w0[c * 3], M[4 * o], fmaf(a.w0[c * 3 + 1], M[4 * o + 1],
+               fmaf(a.w0[c * 3 + 2], M[4 * o + 2], a.b0[c] * M[4 * o + 3])));
+    } else if (col < C * C + C) {
+      v = 0.f;                                      // dbc0 comes from the DC mode (below)
+    } else {
+      const int t = col - (C * C + C);
+      const int c = t < 3 * C ? t / 3 : t - 3 * C, j = t < 3 * C ? t - 3 * c : 3;
+      v = 0.f;
+#pragma unroll
+      for (int o = 0; o < C; ++o) v = fmaf(a.wc[o * C + c], M[4 * o + j], v);
+    }
+    a.pl[((int64_t)a.nspec + row) * kLgRow + col] = v;
+    return;
+  }
+  // sample slice by, modes bx: thread (k, o, j), j fastest (G's order)
+  __shared__ float red[4][4 * C + C];
+  const int bx = b % a.gx, by = b / a.gx;
+  const int t = bx * kBlock + threadIdx.x;
+  const int nmo = a.m2 * C * kCsK1;
+  const bool live = t < nmo;
+  const int tt = live ? t : 0;
+  const int j = tt % kCsK1, o = (tt / kCsK1) % C, k = tt / (kCsK1 * C);
+  const int nsz = (a.Bn + a.ns - 1) / a.ns;
+  const int n0 = by * nsz, n1 = min(a.Bn, n0 + nsz);
+  double rur = 0.0, rui = 0.0, r1r = 0.0, r1i = 0.0;
+  if (live) {
+    const int sG = a.m2 * C * kCsK1, sU = a.m2 * kCsK1;
+    const float2* gp = a.G + ((int64_t)(n0 * a.m2 + k) * C + o) * kCsK1 + j;
+    const float2* up = a.U + (int64_t)(n0 * a.m2 + k) * kCsK1 + j;
+#pragma unroll 4
+    for (int n = n0; n < n1; ++n, gp += sG, up += sU) {
+      const float2 g = *gp;
+      const float2 u = *up;
+      rur = fma((double)u.x, (double)g.x, fma((double)u.y, (double)g.y, rur));
+      rui = fma((double)u.x, (double)g.y, fma(-(double)u.y, (double)g.x, rui));
+      r1r += (double)g.x;
+      r1i += (double)g.y;
+    }
+  }
+  float acc[4 * C + C];                             // dA[c][0..3], then dbc0[o'] (o' = o only)
+#pragma unroll
+  for (int e = 0; e < 4 * C + C; ++e) acc[e] = 0.f;
+  if (live) {
+    const float2* dg = a.Dg2 + (int64_t)k * 3 * kCsK1 + j;
+    const float2 d0 = dg[0], d1 = dg[kCsK1], d2 = dg[2 * kCsK1];
+    const int64_t total = (int64_t)a.m2 * kCsK1 * C * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const double w0u = a.w0[c * 3], w0x = a.w0[c * 3 + 1], w0y = a.w0[c * 3 + 2], w0b = a.b0[c];
+      const double gr = w0x * d0.x + w0y * d1.x + w0b * d2.x;
+      const double gi = w0x * d0.y + w0y * d1.y + w0b * d2.y;
+      // conj(Gam) R1 = (gr - i gi)(r1r + i r1i)
+      const double wr = w0u * rur + gr * r1r + gi * r1i;
+      const double wi = w0u * rui + gr * r1i - gi * r1r;
+      const int64_t idx = ((int64_t)(k * kCsK1 + j) * C + c) * C + o;
+      a.dWp[(int64_t)by * total + idx] = make_float2((float)wr, (float)wi);
+      const float2 w = a.Wt[idx];
+      acc[4 * c] = (float)(rur * w.x + rui * w.y);
+      const double qr = r1r * w.x + r1i * w.y, qi = r1r * w.y - r1i * w.x;   // conj(R1) W
+      acc[4 * c + 1] = (float)(d0.x * qr - d0.y * qi);
+      acc[4 * c + 2] = (float)(d1.x * qr - d1.y * qi);
+      acc[4 * c + 3] = (float)(d2.x * qr - d2.y * qi);
+    }
+  }
+  // kept row 0 is frequency 0 (kept_rows), column mode k = 0: the plain sum of dz0[o], scaled
+  // c_0 / (P1 P2) by the adjoint colmix
+  const bool dc = live && k == 0 && j == 0;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int oo = 0; oo < C; ++oo) acc[4 * C + oo] = (dc && o == oo) ? (float)r1r * a.p1p2 : 0.f;
+#pragma unroll
+  for (int e = 0; e < 4 * C + C; ++e) {
+    const float s = wave_sum(acc[e]);
+    if (lane == 0) red[wave][e] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < kLgRow) {
+    const int col = threadIdx.x;
+    float v = 0.f;
+    if (col >= C * C) {
+      // dbc0 [o] <- acc 16 + o; dfc0W [c][j] <- acc 4 c + j; dfc0b [c] <- acc 4 c + 3
+      int e;
+      if (col < C * C + C) e = 4 * C + (col - C * C);
+      else if (col < C * C + 4 * C) { const int q = col - (C * C + C); e = 4 * (q / 3) + q % 3; }
+      else e = 4 * (col - (C * C + 4 * C)) + 3;
+      v = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
+    }
+    a.pl[(int64_t)b * kLgRow + col] = v;
+  }
+}
+
+// partial rows of blindno_liftgrad_spec (each of 36 floats) for ns sample slices and nrow_m rows
+// of moments
+BLINDNO_API int blindno_liftgrad_rows(int C, int m2, int ns, int nrow_m) {
+  if (C != kLgC || m2 < 1 || ns < 1 || nrow_m < 0) return 0;
+  return (int)cdiv((int64_t)m2 * C * kCsK1, kBlock) * ns + nrow_m;
+}
+
+// The first layer's gradients as partial rows (see liftgrad_kernel): G (Bn, m2, C, K1), U (Bn,
+// m2, K1), Wt (m2, K1, C, C) complex; Dg2 (m2, 3, K1) complex; w0 (C, 3), b0 (C) fc0; wc (C, C) the
+// layer's 1x1 conv; pw (nrow_m, npw) with the moments at columns mcol .. mcol + 4 C - 1.  Writes
+// dWp (ns, m2 K1 C C) complex and pl (blindno_liftgrad_rows, 36); both are finished by
+// blindno_reduce_partials.  C = 4, K1 = 24.  mX / mG / mOut / mshp / nmj: spectral weight
+// gradients hosted by the launch, as blindno_rowidft_bwd_lift_zc_mix takes them.
+BLINDNO_API int blindno_liftgrad_spec(const float* G, const float* U, const float* Wt,
+                                      const float* Dg2, const float* w0, const float* b0,
+                                      const float* wc, const float* pw, int nrow_m, int npw,
+                                      int mcol, float* dWp, float* pl, int Bn, int C, int P1, int P2,
+                                      int m1, int m2, int ns, const void* const* mX,
+                                      const void* const* mG, void* const* mOut, const int* mshp,
+                                      int nmj, void* stream) {
+  if (!G || !U || !Wt || !Dg2 || !w0 || !b0 || !wc || !pw || !dWp || !pl || C != kLgC || Bn < 1 ||
+      m1 != 12 || kept_rows_count(m1, P1) != kCsK1 || m2 < 1 || m2 > 16 || ns < 1 || ns > Bn ||
+      nrow_m < 1 || mcol < 0 || npw < mcol + 4 * C || nmj < 0 || nmj > 2 ||
+      (int64_t)Bn * m2 * C * kCsK1 >= INT32_MAX)
+    return (int)hipErrorInvalidValue;
+  LiftGradArgs a{};
+  a.G = (const float2*)G; a.U = (const float2*)U; a.Wt = (const float2*)Wt; a.Dg2 = (const float2*)Dg2;
+  a.w0 = w0; a.b0 = b0; a.wc = wc; a.pw = pw; a.dWp = (float2*)dWp; a.pl = pl;
+  a.Bn = Bn; a.m2 = m2; a.ns = ns;
+  a.gx = (int)cdiv((int64_t)m2 * C * kCsK1, kBlock);
+  a.nrow_m = nrow_m; a.npw = npw; a.mcol = mcol;
+  a.nspec = a.gx * ns;
+  a.nmrow = (int)cdiv((int64_t)nrow_m * kLgRow, kBlock);
+  a.p1p2 = (float)P1 * (float)P2;
+  int64_t blocks = 0;
+  for (int q = 0; q < nmj; ++q) {
+    const int* sh = mshp + 7 * q;
+    const int mBn = sh[0], Ci = sh[1], Co = sh[2], K1 = sh[3], mm2 = sh[4], nsq = sh[5], Gw = sh[6];
+    const int64_t total = (int64_t)mm2 * K1 * Ci * Co;
+    if (mBn < 1 || Ci < 1 || Co < 1 || K1 < 1 || mm2 < 1 || nsq < 1 || Gw < 1 || mBn % Gw ||
+        total >= INT32_MAX / 2 || !mX[q] || !mG[q] || !mOut[q])
+      return (int)hipErrorInvalidValue;
+    MixWgradJob& m = a.mj[q];
+    m = MixWgradJob{};
+    m.X = (const float2*)mX[q];
+    m.Gs = (const float2*)mG[q];
+    m.out = (float2*)mOut[q];
+    m.Bn = mBn; m.Ci = Ci; m.Co = Co; m.K1 = K1; m.m2 = mm2;
+    m.gx = (int)cdiv(total, kBlock);
+    m.gy = nsq;
+    m.gz = Gw;
+    a.mcum[q] = (int)blocks;
+    blocks += (int64_t)m.gx * nsq * Gw;
+  }
+  a.mcum[nmj] = (int)blocks;
+  a.nmj = nmj;
+  if (blocks + a.nspec + a.nmrow >= INT32_MAX) return (int)hipErrorInvalidValue;
+  liftgrad_kernel<<<(unsigned)(a.nspec + a.nmrow + blocks), kBlock, 0, (hipStream_t)stream>>>(a);
   return (int)hipGetLastError();
 }

@@ -636,8 +636,12 @@ __device__ unsigned long long g_rowfuse_probe[8192 * 8];
 // snapshots = 2080 items: 75 us, where 2000 items took 56).  The MODE 0 ZY / CD kernels take a
 // 3-wave budget (one column tile per step) when their items fit 3072 slots but not 2048
 // DZB (MODE 1): dz = lw_l ghat v formed on load (SpecCol.dzg / dzl; the dz argument is v)
+// MG (MODE 1, no LIFT: the adjoint of the layer after the encoder's first): the lift moments
+// M[o][j] = sum over the N1 x N2 crop of dx[o] in_j, in = (u, gx, gy, 1) read through bl as the
+// LIFT forms read them, as 16 more columns of the partial row; the dx store is skipped when out
+// is NULL (the first layer's gradients then follow from M and spectra: liftgrad_kernel)
 template <int MODE, int ACT, int WG, int LIFT, int RD, int S, int NH, bool HW_ = true, int NSC = 0,
-          bool ZY = false, bool CD = false, int ZW = 0, bool DZB = false>
+          bool ZY = false, bool CD = false, int ZW = 0, bool DZB = false, bool MG = false>
 __global__ __launch_bounds__(256, ZW > 0 ? ZW : 1)
 void rowfuse_kernel(
     const float* __restrict__ Z, const float* __restrict__ xs, const float* __restrict__ dz,
@@ -755,7 +759,10 @@ void rowfuse_kernel(
     for (int j = 0; j < 3; ++j) w0[o][j] = LIFT ? bl.w0[o * 3 + j] : 0.f;
   }
   constexpr int NWC = WG ? C * C + C : 0;          // [o][i] dWc, then dbc
-  constexpr int NWL = (LIFT && MODE == 1) ? 4 * C : 0;   // [c][j] dW0, then db0
+  static_assert(!MG || (MODE == 1 && !LIFT && WG), "MG: the weight-gradient adjoint without the lift");
+  constexpr bool BLIN = LIFT || MG;                // the snapshot and grid rows are read (bl)
+  // LIFT: [c][j] dW0, then db0; MG: M[o][j], j over (u, gx, gy, 1)
+  constexpr int NWL = ((LIFT && MODE == 1) || MG) ? 4 * C : 0;
   constexpr int NW = NWC + NWL > 0 ? NWC + NWL : 1;
   float wacc[NW];
 #pragma unroll
@@ -806,8 +813,8 @@ void rowfuse_kernel(
     const int64_t fbase = (int64_t)n * C * HW + (int64_t)h * P2;
     const float* urow = bl.X;
     const float* grow = bl.grid;
-    const bool lrow = LIFT && h < bl.N1;
-    if (LIFT && lrow) {
+    const bool lrow = BLIN && h < bl.N1;
+    if (BLIN && lrow) {
       const int b = n / bl.L, l = n - (n / bl.L) * bl.L;
       urow = bl.X + (((int64_t)b * bl.T + bl.idx[l]) * bl.N1 + h) * bl.N2;
       grow = bl.grid + (int64_t)h * bl.N2 * 2;
@@ -854,7 +861,7 @@ void rowfuse_kernel(
         }
         o.lok[hf] = false;
         o.u[hf] = o.g0[hf] = o.g1[hf] = zero4;
-        if (LIFT) {
+        if (BLIN) {
           o.lok[hf] = lrow && w < bl.N2;
           const int wl = o.lok[hf] ? w : 0;
           const f32x4 u = *reinterpret_cast<const f32x4*>(urow + wl);
@@ -967,9 +974,18 @@ void rowfuse_kernel(
                   wacc[NWC + 3 * C + c] += v;
                 }
               }
+              if constexpr (MG) {
+                // off the crop u, gx, gy are zero already (load); the ones column is lok
+                const float gx = r < 2 ? cur.g0[hf][2 * r] : cur.g1[hf][2 * r - 4];
+                const float gy = r < 2 ? cur.g0[hf][2 * r + 1] : cur.g1[hf][2 * r - 3];
+                wacc[NWC + 4 * c] = fmaf(v, cur.u[hf][r], wacc[NWC + 4 * c]);
+                wacc[NWC + 4 * c + 1] = fmaf(v, gx, wacc[NWC + 4 * c + 1]);
+                wacc[NWC + 4 * c + 2] = fmaf(v, gy, wacc[NWC + 4 * c + 2]);
+                wacc[NWC + 4 * c + 3] += cur.lok[hf] ? v : 0.f;
+              }
               dg[r] = v;
             }
-            if (!LIFT) *reinterpret_cast<f32x4*>(out + fbase + c * HW + w) = dg;
+            if (!LIFT && (!MG || out)) *reinterpret_cast<f32x4*>(out + fbase + c * HW + w) = dg;
             if (RD) ya[c] = dg;
           }
         }
@@ -1181,7 +1197,9 @@ RowinvGeom rowinv_geom(int Bn, int C, int P1, int P2, int m2) {
 
 // ZC: the column pass folded in (colspec.h; sc.Y for ZY, sc.part for CD with the next row
 // DFT): the transposed C = 4 kernel only, m2 = 12, with the 1x1 conv; no fallback
-template <int MODE, int ACT, int WG, int LIFT = 0, bool ZC = false>
+// MG: the lift moments in the adjoint's partial row (rowfuse_kernel MG; ZC with the previous
+// layer's partials only; bl gives the snapshots and the grid; out may be NULL)
+template <int MODE, int ACT, int WG, int LIFT = 0, bool ZC = false, bool MG = false>
 int rowinv_launch(const float* Z, const float* xs, const float* dz, const float* wc,
                   const float* bc, float* out, const float* TB, float* partial, int nblocks,
                   int Bn, int C, int P1, int P2, int m2, hipStream_t st, BagLift bl = BagLift{},
@@ -1213,7 +1231,8 @@ int rowinv_launch(const float* Z, const float* xs, const float* dz, const float*
                               (!sc.part || (rd.Tp && sc.nblk == P1 / 16)) && (sc.Y || sc.part));
     if (ZC && !(rowfuse_shape(Bn, C, P1, P2, m2) && zc_ok)) return (int)hipErrorInvalidValue;
     if (rowfuse_shape(Bn, C, P1, P2, m2) && G == 1 && al(Z) && al(xs) && al(dz) && al(out) &&
-        dN2 % 4 == 0 && rd_ok && zc_ok && (!LIFT || (bl.N2 % 4 == 0 && al(bl.X) && al(bl.grid)))) {
+        dN2 % 4 == 0 && rd_ok && zc_ok &&
+        (!(LIFT || MG) || (bl.N2 % 4 == 0 && al(bl.X) && al(bl.grid)))) {
       const int NT = P2 / 16, S = m2 / 2;
       const bool rdx = rd.At || (ZC && sc.part);          // the next row DFT taken in the pass
       size_t shf = sizeof(float) * ((size_t)NT * 64 * S + (rdx ? (size_t)NT * 16 * rd.Npad : 0));
@@ -1254,7 +1273,21 @@ int rowinv_launch(const float* Z, const float* xs, const float* dz, const float*
 #define RF(RD_, S_) RFX(RD_, S_, false, false)
 #define RF_S(RD_) \
   do { if (S == 2) RF(RD_, 2); else if (S == 4) RF(RD_, 4); else if (S == 6) RF(RD_, 6); else RF(RD_, 8); } while (0)
-      if constexpr (ZC) {
+      if constexpr (MG) {
+        static_assert(ZC && MODE == 1 && WG == 1 && LIFT == 0, "MG: the folded adjoint with its weight gradient");
+        if (!sc.part || rd.act || !wc || !bl.X || !bl.idx || !bl.grid) return (int)hipErrorInvalidValue;
+        // the two-wave register budget explicitly (ZW = 2): the grid (zc_blocks1) holds two waves
+        // per SIMD, and the moments' operands and sums put the unconstrained build past 256
+        // (v220 + a48, one wave).  Under the budget: v252, a0, no VGPR spill -- a few registers
+        // of headroom only, so re-check tools/res_usage.sh after any toolchain or kernel change
+        // (a VGPR spill here would be silent)
+        if (sc.dzg)
+          rowfuse_kernel<MODE, ACT, WG, LIFT, 1, 6, ROWFUSE_NH1, true, 0, true, true, 2, true, true>
+              <<<nblocks, 256, shf, st>>>(Z, xs, dz, wc, bc, out, TB, partial, Bn, P1, P2, bl, dN1, dN2, rd, sc);
+        else
+          rowfuse_kernel<MODE, ACT, WG, LIFT, 1, 6, ROWFUSE_NH1, true, 0, true, true, 2, false, true>
+              <<<nblocks, 256, shf, st>>>(Z, xs, dz, wc, bc, out, TB, partial, Bn, P1, P2, bl, dN1, dN2, rd, sc);
+      } else if constexpr (ZC) {
         // ZY always; CD with the next row DFT (act: of GELU(field)); m2 = 12 (zc_ok); the 3-wave
         // budget (sc.w3: one column tile per step in the forward) chosen by the caller
         if (MODE == 0 && sc.w3) {
@@ -1293,7 +1326,7 @@ int rowinv_launch(const float* Z, const float* xs, const float* dz, const float*
   // the folded column pass (Z == NULL, Y in sc) exists only in the transposed kernel: a launch-time
   // gate that failed (crop width not in whole float4s, unaligned base) is refused, not sent on to
   // the general kernel, which would read Z
-  if (ZC) return (int)hipErrorInvalidValue;
+  if (ZC || MG) return (int)hipErrorInvalidValue;
   // the general kernel's own geometry also where the shape suits rowfuse but a launch-time gate
   // (G, alignment, crop width) sent it here; nblocks stays the caller's (it sized the partials,
   // and the persistent general kernel strides its items over any grid)
@@ -1702,6 +1735,67 @@ BLINDNO_API int blindno_rowidft_bwd_zc_bag(const float* Y, const float* v, const
                                            P2, m2, st, BagLift{}, 1, 0, Ho, Wo, rd, sc);
   return rowinv_launch<1, 0, 1, 0, true>(nullptr, xsrc, v, wc, nullptr, dx, tb, partial, nb, Bn, C, P1,
                                          P2, m2, st, BagLift{}, 1, 0, Ho, Wo, rd, sc);
+}
+
+// blindno_rowidft_bwd_zc / _zc_bag for the layer after the encoder's first (weight-gradient and
+// column-DFT partials required), whose partial rows also carry the lift moments
+//   M[o][j] = sum_{n, p in the N1 x N2 crop} dx[n][o][p] in_j[n][p],  in = (u, gx, gy, 1),
+// u = X[b][idx[l]] (n = b L + l), (gx, gy) = grid (N1, N2, 2): partial (nchunk, C C + C + 4 C),
+// columns C C + C + 4 o + j (nchunk = blindno_colspec_bwd_nchunk).  dx may be NULL: the field is
+// then not stored (its column-DFT partials and the moments are all the first layer's gradients
+// take, blindno_liftgrad_spec).  N2 % 4 == 0, X and grid 16-byte aligned.
+BLINDNO_API int blindno_rowidft_bwd_zc_m(const float* Y, const float* dz, const float* wc,
+                                         const float* xsrc, float* dx, const float* tb,
+                                         const float* tab, float* part, const float* Tp,
+                                         float* partial, const float* X, const int* idx,
+                                         const float* grid, int B, int T, int L, int N1, int N2,
+                                         int C, int P1, int P2, int m1, int m2, int act, int dN1,
+                                         int dN2, void* stream) {
+  const int Bn = B * L;
+  if (B < 1 || L < 1 || T < 1 || !blindno_colspec_ok(Bn, C, P1, P2, m1, m2) || !Y || !dz || !xsrc ||
+      !tab || !part || !Tp || !partial || !wc || !X || !idx || !grid || dN1 < 1 || dN1 > P1 ||
+      dN2 < 1 || dN2 > P2 || N1 < 1 || N1 > P1 || N2 < 1 || N2 > P2 || N2 % 4)
+    return (int)hipErrorInvalidValue;
+  const int nb = zc_blocks1(Bn * (P1 / 16));
+  hipStream_t st = (hipStream_t)stream;
+  const BagLift bl{X, idx, grid, nullptr, nullptr, T, L, N1, N2};
+  const RowDftNext rd{nullptr, Tp, ((2 * m2 + 15) / 16) * 16, 0};
+  const SpecCol sc = spec_col(Y, part, tab, P1);
+  if (act)
+    return rowinv_launch<1, 1, 1, 0, true, true>(nullptr, xsrc, dz, wc, nullptr, dx, tb, partial, nb, Bn,
+                                                 C, P1, P2, m2, st, bl, 1, 0, dN1, dN2, rd, sc);
+  return rowinv_launch<1, 0, 1, 0, true, true>(nullptr, xsrc, dz, wc, nullptr, dx, tb, partial, nb, Bn, C,
+                                               P1, P2, m2, st, bl, 1, 0, dN1, dN2, rd, sc);
+}
+
+BLINDNO_API int blindno_rowidft_bwd_zc_bag_m(const float* Y, const float* v, const float* ghat,
+                                             const float* lw, const float* wc, const float* xsrc,
+                                             float* dx, const float* tb, const float* tab,
+                                             float* part, const float* Tp, float* partial,
+                                             const float* X, const int* idx, const float* grid,
+                                             int B, int T, int L, int N1, int N2, int C, int P1,
+                                             int P2, int m1, int m2, int act, int Ho, int Wo,
+                                             void* stream) {
+  const int Bn = B * L;
+  if (B < 1 || L < 1 || T < 1 || !blindno_colspec_ok(Bn, C, P1, P2, m1, m2) || !Y || !v || !ghat ||
+      !xsrc || !tab || !part || !Tp || !partial || !wc || !X || !idx || !grid || Ho < 1 || Ho > P1 ||
+      Wo < 1 || Wo > P2 || Wo % 4 || N1 < 1 || N1 > P1 || N2 < 1 || N2 > P2 || N2 % 4)
+    return (int)hipErrorInvalidValue;
+  const int nb = zc_blocks1(Bn * (P1 / 16));
+  hipStream_t st = (hipStream_t)stream;
+  const BagLift bl{X, idx, grid, nullptr, nullptr, T, L, N1, N2};
+  const RowDftNext rd{nullptr, Tp, ((2 * m2 + 15) / 16) * 16, 0};
+  SpecCol sc = spec_col(Y, part, tab, P1);
+  sc.dzg = ghat;
+  sc.dzl = lw;
+  sc.dzU = L;
+  sc.dzWo = Wo;
+  sc.dzS = Ho * Wo;
+  if (act)
+    return rowinv_launch<1, 1, 1, 0, true, true>(nullptr, xsrc, v, wc, nullptr, dx, tb, partial, nb, Bn, C,
+                                                 P1, P2, m2, st, bl, 1, 0, Ho, Wo, rd, sc);
+  return rowinv_launch<1, 0, 1, 0, true, true>(nullptr, xsrc, v, wc, nullptr, dx, tb, partial, nb, Bn, C,
+                                               P1, P2, m2, st, bl, 1, 0, Ho, Wo, rd, sc);
 }
 
 // blindno_rowidft_bwd_lift with Z built from Y

@@ -30,6 +30,10 @@ extern "C" {
  * Ws (16, 8), bs (16), Wq / Wk / Wv (8, 8) are shared by the heads; Wo (32, 32), bo (32);
  * temperature (4).  y, res (S, 32, N) planes; res may be NULL.
  *
+ * The kernels read N = H W points per snapshot and never the plane's shape, so the 3D structured
+ * mesh (Physics_Attention_Structured_Mesh_3D, model/Physics_Attention.py:119-175, after its two
+ * 3x3x3 convolutions) runs on the same entries: a grid (H, W, D) is passed as (H, W D).
+ *
  * Three launches: a slice pass (a thread per point; w stored as (S, 4, 16, N) planes, partials of
  * norm and the unnormalised tokens per workgroup of 256 points), a token pass per (s, h) (partials
  * added in index order; writes tok (S, 4, 16, 8), norm (S, 4, 16), A (S, 4, 16, 16), otok

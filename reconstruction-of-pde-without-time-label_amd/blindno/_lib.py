@@ -292,6 +292,16 @@ SIGNATURES_PHYSATTN = {
     "blindno_ln_planes_bwd": "ppppppppp" + "iii" + "s",
 }
 
+# include/blindno_planemlp.h: the fused per-point MLP over channel planes (csrc/planemlp.hip);
+# every activation pointer is followed by its int64 stride between snapshots
+SIGNATURES_PLANEMLP = {
+    "blindno_plane_mlp_ok": "iiii",
+    "blindno_plane_mlp_nblk": "i",
+    "blindno_plane_mlp_fwd": "pl" + "pppppp" + "pl" + "pl" + "pp" + "iiiii" + "f" + "s",
+    "blindno_plane_mlp_bwd_scratch_floats": "iiiii",
+    "blindno_plane_mlp_bwd": "pl" + "pl" + "ppppp" + "pp" + "p" + "pl" + "pppppp" + "iiiii" + "s",
+}
+
 # entry points returning int64_t (byte counts) instead of an error code / int count
 RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))} | \
     {n for n in SIGNATURES_GPE3D if n.endswith(("_doubles", "_launches"))} | \
@@ -302,7 +312,8 @@ RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))} | \
     {n for n in SIGNATURES_GPE2D if n.endswith(("_doubles", "_launches"))} | \
     {n for n in SIGNATURES_BAG3D if n.endswith("_floats")} | \
     {n for n in SIGNATURES_NIOATTN if n.endswith("_floats")} | \
-    {n for n in SIGNATURES_PHYSATTN if n.endswith("_floats")}
+    {n for n in SIGNATURES_PHYSATTN if n.endswith("_floats")} | \
+    {n for n in SIGNATURES_PLANEMLP if n.endswith("_floats")}
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_int64, "f": ctypes.c_float,
        "d": ctypes.c_double, "s": ctypes.c_void_p}
@@ -331,7 +342,7 @@ def load():
                           **SIGNATURES_BAG3D, **SIGNATURES_GPE3D, **SIGNATURES_FPE_ERR,
                           **SIGNATURES_GPE3D_ERR, **SIGNATURES_GPE2D_ERR,
                           **SIGNATURES_NIOATTN, **SIGNATURES_UNET3D,
-                          **SIGNATURES_PHYSATTN}.items():
+                          **SIGNATURES_PHYSATTN, **SIGNATURES_PLANEMLP}.items():
             fn = getattr(lib, name)
             fn.argtypes = [_CT[c] for c in sig]
             fn.restype = ctypes.c_int64 if name in RET64 else ctypes.c_int
@@ -345,7 +356,8 @@ def exported_symbols():
     return (list(SIGNATURES) + list(SIGNATURES_CONV3D) + list(SIGNATURES_FPE) + list(SIGNATURES_GPE2D) +
             list(SIGNATURES_BAG3D) + list(SIGNATURES_GPE3D) + list(SIGNATURES_FPE_ERR) +
             list(SIGNATURES_GPE3D_ERR) + list(SIGNATURES_GPE2D_ERR) + list(SIGNATURES_NIOATTN) +
-            list(SIGNATURES_UNET3D) + list(SIGNATURES_PHYSATTN) + ["blindno_error_string"])
+            list(SIGNATURES_UNET3D) + list(SIGNATURES_PHYSATTN) + list(SIGNATURES_PLANEMLP) +
+            ["blindno_error_string"])
 
 
 def stream_ptr(device=None):

@@ -1,7 +1,8 @@
 """Snapshot-bag (time-label-free) models: NIOFP2D_FNO, NIOFP_FNO, NIOFP2D, NIOFP2D_attn,
 NIOFP2D_Trans, NIOFP, NIOFP_schrodinger, NIOFP3D -- drop-in for the reference's NIOModules -- and
-NIOFP3D_FNO, the
-project's own 3D FNO-NIO (the reference has no such class).
+NIOFP3D_FNO and
+NIOFP3D_Trans, the project's own 3D FNO-NIO and 3D Transolver-NIO (the reference has no such
+classes).
 
 Same constructor signatures, attribute names and initialisation order as
 2d_FPE/NIOModules.py:14-83,508-581, 2d_Non_conservative_FPE/NIOModules.py:13-82,503-577,
@@ -25,6 +26,7 @@ from .deeponet import FFN, DeepOnetNoBiasOrg
 from .encoders import Encoder, Encoder2D, Encoder3D, Encoder3D_down
 from .fno import FNO1d, FNO2d, FNO3d, fno_params
 from .transolver import Transolver2D
+from .transolver3d import Transolver3D
 
 
 def draw_bag(T: int):
@@ -543,6 +545,56 @@ class NIOFP3D_FNO(nn.Module):
         h = ops.bag_encoder3d(self.FNO_input.padding, x, idx_t, lw, grid, self.fc0.weight.data,
                               self.fc0.bias.data, self.FNO_input.params())
         return self.fno(h)
+
+
+class NIOFP3D_Trans(nn.Module):
+    """3D Transolver-NIO: NIOFP2D_Trans on three axes, ending as NIOFP3D_FNO does.  The reference
+    has the 3D Transolver (model/Transolver_Structured_Mesh_3D.py) and no composite around it;
+    this is the project's own, so there is no ``branch`` to keep a checkpoint layout for.
+
+    ``trans_input`` = Transolver3D(space_dim=3, n_layers=3, n_hidden=32, n_head=4, mlp_ratio=1,
+    fun_dim=1, out_dim=1, slice_num=16, H, W, D = grid_shape) encodes every distinct snapshot of
+    the bag from the point features [rho, gx, gy, gz] (it has LayerNorm and no BatchNorm, so a
+    snapshot's encoding does not depend on the rest of the bag); ``fc0`` = Linear(4, width), read
+    through ``.data`` and never trained, maps [gx, gy, gz, bag mean] to the head's width, the bag
+    mean weighted by multiplicity / L; ``fno`` = FNO3d(modes, width, fno_layers, width,
+    output_dim) is the single head."""
+
+    def __init__(self, fno_layers, width, modes, output_dim, device, grid_shape):
+        super().__init__()
+        self.device = device
+        self.fno_layers = fno_layers
+        self.grid_shape = tuple(int(n) for n in grid_shape)
+        if len(self.grid_shape) != 3:
+            raise ValueError(f"NIOFP3D_Trans: grid_shape must be (Nx, Ny, Nz), got {grid_shape}")
+        H, W, D = self.grid_shape
+        self.trans_input = Transolver3D(space_dim=3, n_layers=3, n_hidden=32, dropout=0.0, n_head=4,
+                                        Time_Input=False, mlp_ratio=1, fun_dim=1, out_dim=1,
+                                        slice_num=16, ref=8, unified_pos=False, H=H, W=W, D=D)
+        self.fc0 = nn.Linear(4, width)
+        self.fno = FNO3d(modes=modes, width=width, n_layers=self.fno_layers, input_dim=width,
+                         output_dim=output_dim, device=self.device)
+
+    # parameters that never receive a gradient
+    unused_prefixes = ("trans_input.placeholder", "fc0.")
+
+    def forward(self, x, grid, bag_idx=None):
+        """x (B, T, Nx, Ny, Nz), grid (Nx, Ny, Nz, 3) -> (B, Nx, Ny, Nz, output_dim).  ``bag_idx``
+        overrides the train-mode draw (draw_bag: with replacement); eval mode uses all T
+        snapshots."""
+        ops.require_device(x, grid)
+        n = self.grid_shape
+        if x.dim() != 5 or tuple(x.shape[2:]) != n or tuple(grid.shape) != (*n, 3):
+            raise ValueError(f"NIOFP3D_Trans: built for a {n[0]} x {n[1]} x {n[2]} grid; got x "
+                             f"{tuple(x.shape)} and grid {tuple(grid.shape)}")
+        x, L, lw = _select(self, x, bag_idx, dedup=True)
+        B, P = x.shape[0], n[0] * n[1] * n[2]
+        g = grid.permute(3, 0, 1, 2).unsqueeze(0).expand(B * L, 3, *n)
+        inp = torch.cat((x.reshape(B * L, 1, *n), g), dim=1)          # [rho, gx, gy, gz] planes
+        u = self.trans_input.forward_planes(inp)                      # (B L, 1, Nx, Ny, Nz)
+        h = ops.BagMeanFn.apply(u.reshape(B, L, P), grid.reshape(P, 3), self.fc0.weight.data,
+                                self.fc0.bias.data, lw)
+        return self.fno(h.view(B, *n, -1))
 
 
 class NIOFP(nn.Module):

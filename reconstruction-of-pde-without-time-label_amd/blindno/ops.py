@@ -2867,3 +2867,84 @@ class LayerNormPlanesFn(torch.autograd.Function):
         call("blindno_ln_planes_bwd", ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx),
              ptr(dgamma), ptr(dbeta), ptr(partial), S, C, HW, stream_ptr())
         return dx, dgamma, dbeta, None
+
+
+def plane_mlp_ok(Cin, Chid, Cout, has_ln) -> bool:
+    """The fused plane MLP takes this configuration (blindno_plane_mlp_ok)."""
+    return bool(query("blindno_plane_mlp_ok", int(Cin), int(Chid), int(Cout), int(bool(has_ln))))
+
+
+class PlaneMLPFn(torch.autograd.Function):
+    """The Transolver's token MLP on channel planes in one launch (csrc/planemlp.hip,
+    include/blindno_planemlp.h): x (S, Cin, ...) -> W2 gelu(W1 u + b1) + b2 (+ res) as
+    (S, Cout, ...) planes, u = LayerNorm_C(x) with ``gamma`` / ``beta`` and x without.  Two
+    configurations run (ValueError otherwise): (Cin, Chid, Cout) = (32, 32, 32) with the LayerNorm
+    (a block's ln_2 + mlp + residual) and (4, 64, 32) without (preprocess).  x and res may be
+    channel slices of wider tensors (dimension 1 sliced, the rest dense).  The hidden layer is
+    never stored: the backward recomputes it from x, and only mean / rstd (S, N) are kept."""
+
+    @staticmethod
+    def _planes(t, name):
+        """(tensor, floats between snapshots): t as it is where its planes are dense."""
+        pl = t[0, 0].numel()
+        dense = t[0, 0].is_contiguous() and (t.shape[1] == 1 or t.stride(1) == pl) and \
+            (t.shape[0] == 1 or t.stride(0) >= t.shape[1] * pl)
+        if t.dtype != F32:
+            raise BlindnoError(f"blindno ops are fp32: got {t.dtype} for {name}")
+        if not dense:
+            t = t.contiguous()
+        return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1] * pl)
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, W2, b2, res=None, gamma=None, beta=None, eps=1e-5):
+        require_device(x, W1, b1, W2, b2, res, gamma, beta)
+        if x.dim() < 3 or W1.dim() != 2 or W2.dim() != 2:
+            raise ValueError(f"PlaneMLPFn: x must be (S, Cin, ...) planes and W1, W2 matrices, got x "
+                             f"{tuple(x.shape)}, W1 {tuple(W1.shape)}, W2 {tuple(W2.shape)}")
+        if (gamma is None) != (beta is None):
+            raise ValueError("PlaneMLPFn: gamma and beta come together")
+        S, Cin = x.shape[:2]
+        N = x[0, 0].numel() if S > 0 else 0
+        Chid, Cout = W1.shape[0], W2.shape[0]
+        ln = gamma is not None
+        if (not plane_mlp_ok(Cin, Chid, Cout, ln) or tuple(W1.shape) != (Chid, Cin) or
+                tuple(W2.shape) != (Cout, Chid) or tuple(b1.shape) != (Chid,) or
+                tuple(b2.shape) != (Cout,) or (ln and (gamma.numel() != Cin or beta.numel() != Cin))):
+            raise ValueError("PlaneMLPFn: the HIP kernels take (Cin, Chid, Cout) = (32, 32, 32) with a "
+                             "LayerNorm and (4, 64, 32) without; got "
+                             f"({Cin}, {Chid}, {Cout}), LayerNorm {'on' if ln else 'off'}")
+        if res is not None and tuple(res.shape) != (S, Cout, *x.shape[2:]):
+            raise ValueError(f"PlaneMLPFn: res must be {(S, Cout, *x.shape[2:])}, got {tuple(res.shape)}")
+        x, xs = PlaneMLPFn._planes(x, "x")
+        rs = 0
+        if res is not None:
+            res, rs = PlaneMLPFn._planes(res, "res")
+        W1, b1, W2, b2, gamma, beta = (_c(t) for t in (W1, b1, W2, b2, gamma, beta))
+        y = _empty(S, Cout, *x.shape[2:], like=x)
+        mean = _empty(S, N, like=x) if ln else None
+        rstd = _empty(S, N, like=x) if ln else None
+        call("blindno_plane_mlp_fwd", ptr(x), xs, ptr(gamma), ptr(beta), ptr(W1), ptr(b1), ptr(W2),
+             ptr(b2), ptr(res), rs, ptr(y), Cout * N, ptr(mean), ptr(rstd), S, N, Cin, Chid, Cout,
+             float(eps), stream_ptr())
+        ctx.save_for_backward(x, W1, b1, W2, gamma, beta, mean, rstd)
+        ctx.xs = xs
+        ctx.has_res = res is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, W1, b1, W2, gamma, beta, mean, rstd = ctx.saved_tensors
+        S, Cin = x.shape[:2]
+        N = x[0, 0].numel()
+        Chid, Cout = W1.shape[0], W2.shape[0]
+        dy = _c(dy)
+        scratch = _empty(query("blindno_plane_mlp_bwd_scratch_floats", S, N, Cin, Chid, Cout), like=dy)
+        dx = _empty(*x.shape, like=dy)
+        dW1, db1, dW2 = torch.empty_like(W1), torch.empty_like(b1), torch.empty_like(W2)
+        db2 = _empty(Cout, like=dy)
+        dgamma = torch.empty_like(gamma) if gamma is not None else None
+        dbeta = torch.empty_like(beta) if beta is not None else None
+        call("blindno_plane_mlp_bwd", ptr(dy), Cout * N, ptr(x), ctx.xs, ptr(gamma), ptr(beta), ptr(W1),
+             ptr(b1), ptr(W2), ptr(mean), ptr(rstd), ptr(scratch), ptr(dx), Cin * N, ptr(dW1), ptr(db1),
+             ptr(dW2), ptr(db2), ptr(dgamma), ptr(dbeta), S, N, Cin, Chid, Cout, stream_ptr())
+        return dx, dW1, db1, dW2, db2, (dy if ctx.has_res else None), dgamma, dbeta, None

@@ -793,7 +793,9 @@ int blindno_spectral_conv1d_bwd(const float* dy, const float* saved, const float
  * Depthwise convolution of ConvNeXtBlock (nn.Conv2d(C, C, 7, padding=3, groups=C), :1047;
  * Conv1d(C, C, 7, padding=3, groups=C), 1d_FPE/NIOModules.py:167): x, y (N, C, H, W), w (C, KH, KW),
  * padding (KH/2, KW/2), KH KW <= 49.  bwd_weight: dwb (C, KH KW + 1), last column = db; partial:
- * nsplit x C x (KH KW + 1) floats (nsplit = blindno_dwconv_wgrad_nsplit; NULL when 1). */
+ * nsplit x C x (KH KW + 1) floats (nsplit = blindno_dwconv_wgrad_nsplit; NULL when 1).  Any
+ * nsplit >= 1 is accepted (splits past the last pixel contribute +0).  The three entries refuse
+ * the same geometries: every extent >= 1 and KH KW <= 49, before any launch. */
 int blindno_dwconv_fwd(const float* x, const float* w, const float* b, float* y, int N, int C,
                        int H, int W, int KH, int KW, blindno_stream_t stream);
 int blindno_dwconv_bwd_data(const float* dy, const float* w, float* dx, int N, int C, int H,
@@ -817,16 +819,19 @@ int blindno_cnx_pw_bwd(const float* dy, const float* xd, const float* lw, const 
                        float* dparams, float* partial, int nblk, int N, int C, int HW,
                        blindno_stream_t stream);
 /* MaxPool2d(2) / MaxPool1d(2) (:1115, 1d :239): window = stride = KH x KW, floor; arg (NC, Ho, Wo)
- * uint8 index of the window's maximum (first in scan order; a NaN wins). */
+ * uint8 index of the window's maximum (first in scan order; a NaN wins).  Both entries refuse
+ * NC, KH, KW < 1, H < KH, W < KW and KH KW > 255 (arg is a byte). */
 int blindno_maxpool_fwd(const float* x, float* y, uint8_t* arg, int NC, int H, int W, int KH,
                         int KW, blindno_stream_t stream);
 int blindno_maxpool_bwd(const float* dy, const uint8_t* arg, float* dx, int NC, int H, int W,
                         int KH, int KW, blindno_stream_t stream);
 /* ConvTranspose2d(Ci, Co, kernel = stride = 2, output_padding) of the up path (:1130-1134;
  * 1d :258-261 with KH = 1): x (N, Ci, Hi, Wi), w (Ci, Co, KH, KW), y (N, Co, Ho, Wo) with
- * KH Hi <= Ho < KH (Hi + 1) (the extra rows / columns are output_padding).  bwd_weight:
- * dwb = [dW (Ci Co KH KW) | db (Co)], partial blindno_convt_wgrad_nparts(N, Hi, Wi) x
- * (Ci Co KH KW + Co) floats. */
+ * KH Hi <= Ho < KH (Hi + 1), KW Wi <= Wo < KW (Wi + 1) (the extra rows / columns are
+ * output_padding).  bwd_weight: dwb = [dW (Ci Co KH KW) | db (Co)], partial
+ * blindno_convt_wgrad_nparts(N, Hi, Wi) x (Ci Co KH KW + Co) floats (required).  One rule for the
+ * three entries: every extent >= 1 and Ho, Wo in the ranges above, or the call is refused
+ * before any launch (bwd_data and bwd_weight read dy with the forward's geometry). */
 int blindno_convt_fwd(const float* x, const float* w, const float* b, float* y, int N, int Ci,
                       int Hi, int Wi, int Co, int KH, int KW, int Ho, int Wo,
                       blindno_stream_t stream);
@@ -841,10 +846,15 @@ int blindno_convt_bwd_weight(const float* dy, const float* x, float* dwb, float*
  * snapshot features flattened to D = C H W, LayerNorm eps `eps` with gamma lw / beta lb (D).
  * Collapsed to a centred Gram matrix per bag (see csrc/unet.hip).  L <= 480.
  *   save: blindno_tok_attn_save_floats(B, L, D) floats (16-B aligned), written by the forward,
- *         read by the backward; gram: B L L floats; gram_partial: blindno_tok_gram_nchunk(D)
+ *         read by the backward: st (B, L, 4) = (mu, r, c, lo) | xbar (B, L) | A | P (B, L, L) |
+ *         kappa (B) | U (B, D); a token's mean is xbar + lo (lo = mean_d(X - xbar)); gram: B L L floats; gram_partial: blindno_tok_gram_nchunk(D)
  *         x B L L floats (NULL when that is 1).
- *   bwd:  dX (B, L, D) (NULL: none), dlw / dlb (D) (NULL: none); scratch:
- *         blindno_tok_attn_bwd_scratch_floats(B, L) floats (8-B aligned). */
+ *   bwd:  dX (B, L, D) (NULL: none), dlw / dlb (D) (NULL: none; each on its own: exactly one
+ *         of the two may be NULL, the other is still written); scratch:
+ *         blindno_tok_attn_bwd_scratch_floats(B, L) floats (8-B aligned), only touched when dX
+ *         is asked for; its one pad float (next to the float2 tail) is never written.
+ *   Refused before any launch (save stays untouched): B, L, D < 1, L > 480, save or gram NULL,
+ *   a misaligned save / scratch, gram_partial NULL with more than one chunk. */
 int blindno_tok_gram_nchunk(int64_t D);
 int64_t blindno_tok_attn_save_floats(int B, int L, int64_t D);
 int blindno_tok_attn_fwd(const float* X, const float* lw, const float* lb, float* Y, float* save,

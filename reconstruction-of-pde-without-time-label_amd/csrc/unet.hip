@@ -19,7 +19,11 @@
 // (Gc + D x x^T) / sqrt D.  So the forward is: token means, one centred Gram matrix per bag
 // (L x L, reduced over D), O(L^3) bag-local algebra, and a c-weighted sum of centred tokens --
 // nothing of size L x D is written.  Everything is kept in centred quantities (tokens whose
-// mean is large against their spread would otherwise cancel catastrophically).
+// mean is large against their spread would otherwise cancel catastrophically).  A token mean is
+// held as two floats, xbar_t + lo_t (lo_t = mean_d(X_t - xbar_t), in st[t].w): one float leaves
+// the "centred" token with a mean of up to ulp(xbar_t) / 2, which D xbar_l multiplies in the
+// scores.  The scores drop the row constant D x_l^2 (softmax is shift invariant) and are formed
+// from x_t - x_l, so that D x_l x_t is never rounded at its own magnitude.
 // The backward is the exact adjoint.  With g = gamma dYbar, gb = mean(g), centred dots
 // h_t = g.(X_t - x_t), a_l = r_l / L and P = M Gc (saved by the forward):
 //   b_l  = a_l r_l^2 (sum_t M_lt h_t) / D
@@ -233,10 +237,19 @@ __device__ __forceinline__ float cnx_norm(float (&x)[C]) {
 #pragma unroll
   for (int c = 0; c < C; ++c) m += x[c];
   m *= 1.0f / C;
-  float v = 0.f;
+  // the sum of C values that share a large offset rounds at the offset's ulp, not the spread's:
+  // remove the mean that is left in x - m (a sum of small numbers) before squaring
+  float d = 0.f;
 #pragma unroll
   for (int c = 0; c < C; ++c) {
     x[c] -= m;
+    d += x[c];
+  }
+  d *= 1.0f / C;
+  float v = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    x[c] -= d;
     v = fmaf(x[c], x[c], v);
   }
   const float r = 1.0f / sqrtf(v * (1.0f / C) + 1e-6f);
@@ -526,15 +539,23 @@ __global__ __launch_bounds__(kBlock) void convt_wgrad_kernel(
 }
 
 // ---------------------------------------------------------------------- temporal attention
-// token means: xbar[bt] = (1/D) sum_d X[bt][d]  (one workgroup per token)
+// token means: xbar[bt] = (1/D) sum_d X[bt][d] and its low part st[bt].w = (1/D) sum_d
+// (X[bt][d] - xbar[bt])  (one workgroup per token)
 __global__ __launch_bounds__(kBlock) void tok_mean_kernel(const float* __restrict__ X,
-                                                          float* __restrict__ xbar, int64_t D) {
+                                                          float* __restrict__ xbar,
+                                                          float4* __restrict__ st, int64_t D) {
   __shared__ float red[8];
   const float* xp = X + (int64_t)blockIdx.x * D;
   float s = 0.f;
   for (int64_t d = threadIdx.x; d < D; d += blockDim.x) s += xp[d];
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) xbar[blockIdx.x] = s / (float)D;
+  const float m = block_sum(s, red) / (float)D;
+  float r = 0.f;
+  for (int64_t d = threadIdx.x; d < D; d += blockDim.x) r += xp[d] - m;
+  r = block_sum(r, red);
+  if (threadIdx.x == 0) {
+    xbar[blockIdx.x] = m;
+    st[blockIdx.x].w = r / (float)D;
+  }
 }
 
 constexpr int kGramPts = 32;     // points per LDS sub-tile
@@ -545,6 +566,7 @@ constexpr int kGramChunk = 128;  // points per workgroup (one partial): D = 3721
 // blocks of the upper block triangle (blockIdx.y = round of 256 blocks) and mirrors them.
 __global__ __launch_bounds__(kBlock) void tok_gram_kernel(const float* __restrict__ X,
                                                           const float* __restrict__ xbar,
+                                                          const float4* __restrict__ st,
                                                           float* __restrict__ partial, int B,
                                                           int L, int64_t D) {
   extern __shared__ float xs[];          // [L][kGramPts + 1]
@@ -567,7 +589,9 @@ __global__ __launch_bounds__(kBlock) void tok_gram_kernel(const float* __restric
     __syncthreads();
     for (int e = threadIdx.x; e < L * kGramPts; e += blockDim.x) {
       const int t = e / kGramPts, q = e % kGramPts;
-      xs[t * LD + q] = q0 + q < p1 ? Xb[(int64_t)t * D + q0 + q] - xbar[(int64_t)b * L + t] : 0.f;
+      xs[t * LD + q] = q0 + q < p1 ? (Xb[(int64_t)t * D + q0 + q] - xbar[(int64_t)b * L + t]) -
+                                         st[(int64_t)b * L + t].w
+                                   : 0.f;
     }
     __syncthreads();
     if (own) {
@@ -604,7 +628,7 @@ __global__ __launch_bounds__(kBlock) void tok_gram_kernel(const float* __restric
 // Forward bag algebra, one workgroup per (token row l, bag b) -- B L workgroups, every row's
 // L^2 work spread over the workgroup's threads.  In: Gc[b] (L x L), xbar[b] (L).  Out: row l of
 // A[b] = softmax((Gc + D xbar xbar^T) / sqrt D), row l of P[b] = M Gc (M = A + I), and
-// st[b][l] = (mu_l, r_l, ., .) with mu_l = sum_s M_ls xbar_s, var_l = (1/D) sum_s P_ls M_ls.
+// st[b][l] = (mu_l, r_l, ., lo_l) with mu_l = sum_s M_ls xbar_s, var_l = (1/D) sum_s P_ls M_ls.
 constexpr int kRowThreads = 128;
 __global__ __launch_bounds__(kRowThreads) void tok_rows_kernel(const float* __restrict__ Gc,
                                                                const float* __restrict__ xbar,
@@ -618,10 +642,12 @@ __global__ __launch_bounds__(kRowThreads) void tok_rows_kernel(const float* __re
   const float* G = Gc + (int64_t)b * L * L;
   const float* xb = xbar + (int64_t)b * L;
   const float Df = (float)D, isd = 1.0f / sqrtf(Df);
-  const float xl = xb[l];
+  const float xl = xb[l], lol = st[(int64_t)b * L + l].w;
   float mx = -INFINITY;
   for (int t = threadIdx.x; t < L; t += blockDim.x) {
-    const float sc = (G[(int64_t)l * L + t] + Df * xl * xb[t]) * isd;
+    // (Gc_lt + D x_l x_t - D x_l^2) / sqrt D, x = xbar + lo
+    const float dxm = (xb[t] - xl) + (st[(int64_t)b * L + t].w - lol);
+    const float sc = (G[(int64_t)l * L + t] + Df * xl * dxm) * isd;
     arow[t] = sc;
     mx = fmaxf(mx, sc);
   }
@@ -652,7 +678,10 @@ __global__ __launch_bounds__(kRowThreads) void tok_rows_kernel(const float* __re
   mu = block_sum(mu, red);
   if (threadIdx.x == 0) {
     const float var = fmaxf(q / Df, 0.f);
-    st[(int64_t)b * L + l] = make_float4(mu, 1.0f / sqrtf(var + eps), 0.f, 0.f);
+    float4* o = st + (int64_t)b * L + l;        // .w (the mean's low part) stays; other rows read it
+    o->x = mu;
+    o->y = 1.0f / sqrtf(var + eps);
+    o->z = 0.f;
   }
 }
 
@@ -692,8 +721,10 @@ __global__ __launch_bounds__(kBlock) void tok_out_kernel(const float* __restrict
   if (d >= D) return;
   const float* Xb = X + (int64_t)b * L * D + d;
   float acc = 0.f;
-  for (int t = 0; t < L; ++t)
-    acc = fmaf(st[(int64_t)b * L + t].z, Xb[(int64_t)t * D] - xbar[(int64_t)b * L + t], acc);
+  for (int t = 0; t < L; ++t) {
+    const float4 s4 = st[(int64_t)b * L + t];
+    acc = fmaf(s4.z, (Xb[(int64_t)t * D] - xbar[(int64_t)b * L + t]) - s4.w, acc);
+  }
   const float u = acc;
   U[(int64_t)b * D + d] = u;
   Y[(int64_t)b * D + d] = fmaf(lw[d], u, lb[d]);
@@ -703,6 +734,7 @@ __global__ __launch_bounds__(kBlock) void tok_out_kernel(const float* __restrict
 // token b L is also the one that forms gb[b] = mean_d gamma dY)
 __global__ __launch_bounds__(kBlock) void tok_bwd_dot_kernel(const float* __restrict__ X,
                                                              const float* __restrict__ xbar,
+                                                             const float4* __restrict__ st,
                                                              const float* __restrict__ dY,
                                                              const float* __restrict__ lw,
                                                              float* __restrict__ h,
@@ -712,12 +744,12 @@ __global__ __launch_bounds__(kBlock) void tok_bwd_dot_kernel(const float* __rest
   const int bt = blockIdx.x, b = bt / L;
   const float* xp = X + (int64_t)bt * D;
   const float* gp = dY + (int64_t)b * D;
-  const float xm = xbar[bt];
+  const float xm = xbar[bt], lo = st[bt].w;
   float s = 0.f, s2 = 0.f;
   const bool first = bt % L == 0;
   for (int64_t d = threadIdx.x; d < D; d += blockDim.x) {
     const float g = lw[d] * gp[d];
-    s = fmaf(g, xp[d] - xm, s);
+    s = fmaf(g, (xp[d] - xm) - lo, s);
     if (first) s2 += g;
   }
   s = block_sum(s, red);
@@ -777,11 +809,13 @@ __global__ __launch_bounds__(kRowThreads) void tok_bwd_rows_kernel(
 }
 
 // Pass 2, workgroup (t, b): row t of R = (dS + dS^T)/sqrt D - N, N_ts = sum_l M_lt b_l M_ls, and
-// coef[b][t] = (a_t, k_t): a_t = sum_l M_lt alpha_l, k_t = sum_s Q_ts xbar_s - a_t gb.
+// coef[b][t] = (a_t, k_t): a_t = sum_l M_lt alpha_l, k_t = sum_s Q_ts xbar_s (the - a_t gb of the
+// constant term is applied by the dX kernel as a_t (g - gb): a_t g - a_t gb formed from two rounded
+// products leaves noise of ulp(a_t g) where the result is 0, e.g. at D = 1).
 __global__ __launch_bounds__(kRowThreads) void tok_bwd_rrow_kernel(
     const float* __restrict__ A, const float* __restrict__ Wk, const float2* __restrict__ ab,
-    const float* __restrict__ xbar, const float* __restrict__ gbar, float* __restrict__ R,
-    float2* __restrict__ coef, int L, int64_t D) {
+    const float* __restrict__ xbar, float* __restrict__ R, float2* __restrict__ coef, int L,
+    int64_t D) {
   __shared__ float red[4];
   __shared__ float mcol[kMaxTok];
   const int t = blockIdx.x, b = blockIdx.y;
@@ -805,18 +839,20 @@ __global__ __launch_bounds__(kRowThreads) void tok_bwd_rrow_kernel(
     k = fmaf(qv, xbar[(int64_t)b * L + s2], k);
   }
   k = block_sum(k, red);
-  if (threadIdx.x == 0) coef[(int64_t)b * L + t] = make_float2(a, k - a * gbar[b]);
+  if (threadIdx.x == 0) coef[(int64_t)b * L + t] = make_float2(a, k);
 }
 
-// dX[b][t][d] = a_t gamma[d] dY[b][d] + sum_s R_ts (X_s[d] - xbar_s) + k_t; a thread owns kTT
+// dX[b][t][d] = a_t (gamma[d] dY[b][d] - gb) + sum_s R_ts (X_s[d] - xbar_s) + k_t; a thread owns kTT
 // tokens of one point d (R loads are wave-uniform, X_s[d] coalesced over d)
 constexpr int kTT = 8;
 __global__ __launch_bounds__(kBlock) void tok_bwd_dx_kernel(const float* __restrict__ X,
                                                             const float* __restrict__ xbar,
+                                                            const float4* __restrict__ st,
                                                             const float* __restrict__ R,
                                                             const float2* __restrict__ coef,
                                                             const float* __restrict__ lw,
                                                             const float* __restrict__ dY,
+                                                            const float* __restrict__ gbar,
                                                             float* __restrict__ dX, int L,
                                                             int64_t D) {
   const int b = blockIdx.z, t0 = blockIdx.y * kTT;
@@ -826,12 +862,12 @@ __global__ __launch_bounds__(kBlock) void tok_bwd_dx_kernel(const float* __restr
   const float* Rb = R + (int64_t)b * L * L;
   float acc[kTT] = {};
   for (int s = 0; s < L; ++s) {
-    const float xs = Xb[(int64_t)s * D] - xbar[(int64_t)b * L + s];
+    const float xs = (Xb[(int64_t)s * D] - xbar[(int64_t)b * L + s]) - st[(int64_t)b * L + s].w;
 #pragma unroll
     for (int i = 0; i < kTT; ++i)
       if (t0 + i < L) acc[i] = fmaf(Rb[(int64_t)(t0 + i) * L + s], xs, acc[i]);
   }
-  const float g = lw[d] * dY[(int64_t)b * D + d];
+  const float g = lw[d] * dY[(int64_t)b * D + d] - gbar[b];
 #pragma unroll
   for (int i = 0; i < kTT; ++i) {
     const int t = t0 + i;
@@ -878,7 +914,8 @@ BLINDNO_API int blindno_dwconv_wgrad_nsplit(int N, int C, int H, int W) {
 BLINDNO_API int blindno_dwconv_bwd_weight(const float* dy, const float* x, float* dwb,
                                           float* partial, int nsplit, int N, int C, int H, int W,
                                           int KH, int KW, void* stream) {
-  if (N < 1 || C < 1 || KH * KW > kMaxTaps || nsplit < 1 || (nsplit > 1 && !partial))
+  if (N < 1 || C < 1 || H < 1 || W < 1 || KH < 1 || KW < 1 || KH * KW > kMaxTaps || nsplit < 1 ||
+      (nsplit > 1 && !partial))
     return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   float* dst = nsplit > 1 ? partial : dwb;
@@ -945,7 +982,7 @@ BLINDNO_API int blindno_maxpool_fwd(const float* x, float* y, uint8_t* arg, int 
 
 BLINDNO_API int blindno_maxpool_bwd(const float* dy, const uint8_t* arg, float* dx, int NC, int H,
                                     int W, int KH, int KW, void* stream) {
-  if (NC < 1 || KH < 1 || KW < 1 || H < KH || W < KW) return (int)hipErrorInvalidValue;
+  if (NC < 1 || KH < 1 || KW < 1 || KH * KW > 255 || H < KH || W < KW) return (int)hipErrorInvalidValue;
   const int Ho = H / KH, Wo = W / KW;
   const int64_t total = (int64_t)NC * H * W;
   maxpool_bwd_kernel<<<blocks_for(total), kBlock, 0, (hipStream_t)stream>>>(dy, arg, dx, H, W, Ho, Wo,
@@ -953,12 +990,18 @@ BLINDNO_API int blindno_maxpool_bwd(const float* dy, const uint8_t* arg, float* 
   return (int)hipGetLastError();
 }
 
+// One geometry rule for the three convt entries: every extent >= 1 and
+// KH Hi <= Ho < KH (Hi + 1), KW Wi <= Wo < KW (Wi + 1) (output_padding < stride)
+static bool convt_geometry_ok(int N, int Ci, int Hi, int Wi, int Co, int KH, int KW, int Ho, int Wo) {
+  return N >= 1 && Ci >= 1 && Co >= 1 && Hi >= 1 && Wi >= 1 && KH >= 1 && KW >= 1 &&
+         Ho >= (int64_t)KH * Hi && Wo >= (int64_t)KW * Wi && Ho < (int64_t)KH * Hi + KH &&
+         Wo < (int64_t)KW * Wi + KW;
+}
+
 BLINDNO_API int blindno_convt_fwd(const float* x, const float* w, const float* b, float* y, int N,
                                   int Ci, int Hi, int Wi, int Co, int KH, int KW, int Ho, int Wo,
                                   void* stream) {
-  if (N < 1 || Ci < 1 || Co < 1 || Ho < KH * Hi || Wo < KW * Wi || Ho >= KH * Hi + KH ||
-      Wo >= KW * Wi + KW)
-    return (int)hipErrorInvalidValue;
+  if (!convt_geometry_ok(N, Ci, Hi, Wi, Co, KH, KW, Ho, Wo)) return (int)hipErrorInvalidValue;
   const int64_t total = (int64_t)N * Co * Ho * Wo;
   convt_fwd_kernel<<<blocks_for(total), kBlock, 0, (hipStream_t)stream>>>(x, w, b, y, Ci, Hi, Wi, Co,
                                                                         KH, KW, Ho, Wo, total);
@@ -968,7 +1011,7 @@ BLINDNO_API int blindno_convt_fwd(const float* x, const float* w, const float* b
 BLINDNO_API int blindno_convt_bwd_data(const float* dy, const float* w, float* dx, int N, int Ci,
                                        int Hi, int Wi, int Co, int KH, int KW, int Ho, int Wo,
                                        void* stream) {
-  if (N < 1 || Ci < 1 || Co < 1 || Ho < KH * Hi || Wo < KW * Wi) return (int)hipErrorInvalidValue;
+  if (!convt_geometry_ok(N, Ci, Hi, Wi, Co, KH, KW, Ho, Wo)) return (int)hipErrorInvalidValue;
   const int64_t total = (int64_t)N * Ci * Hi * Wi;
   convt_bwd_data_kernel<<<blocks_for(total), kBlock, 0, (hipStream_t)stream>>>(dy, w, dx, Ci, Hi, Wi,
                                                                              Co, KH, KW, Ho, Wo, total);
@@ -984,7 +1027,8 @@ BLINDNO_API int blindno_convt_wgrad_nparts(int N, int Hi, int Wi) {
 BLINDNO_API int blindno_convt_bwd_weight(const float* dy, const float* x, float* dwb,
                                          float* partial, int N, int Ci, int Hi, int Wi, int Co,
                                          int KH, int KW, int Ho, int Wo, void* stream) {
-  if (N < 1 || Ci < 1 || Co < 1 || !partial) return (int)hipErrorInvalidValue;
+  if (!convt_geometry_ok(N, Ci, Hi, Wi, Co, KH, KW, Ho, Wo) || !partial)
+    return (int)hipErrorInvalidValue;
   const int E = Ci * Co * KH * KW + Co;
   const int S = (Hi * Wi + kConvtChunk - 1) / kConvtChunk;
   int gz = (E + kBlock - 1) / kBlock;
@@ -1002,6 +1046,7 @@ BLINDNO_API int blindno_tok_gram_nchunk(int64_t D) {
 
 // Saved state of the temporal attention forward (floats; 16-B aligned base), kept until the
 // backward:  save = [st (4 B L) | xbar (B L) | A (B L L) | P (B L L) | kappa (B) | U (B D)]
+// st[b][l] = (mu_l, r_l, c_l, lo_l), the token mean being xbar + lo
 // gram: B L L floats; gram_partial: blindno_tok_gram_nchunk(D) x B L L floats (NULL if 1)
 BLINDNO_API int64_t blindno_tok_attn_save_floats(int B, int L, int64_t D) {
   return (int64_t)B * L + 2 * (int64_t)B * L * L + 4 * (int64_t)B * L + B + (int64_t)B * D;
@@ -1010,7 +1055,11 @@ BLINDNO_API int64_t blindno_tok_attn_save_floats(int B, int L, int64_t D) {
 BLINDNO_API int blindno_tok_attn_fwd(const float* X, const float* lw, const float* lb, float* Y,
                                      float* save, float* gram_partial, float* gram, int B, int L,
                                      int64_t D, float eps, void* stream) {
-  if (B < 1 || L < 1 || L > kMaxTok || D < 1 || !save || !gram) return (int)hipErrorInvalidValue;
+  // every refusal comes before the first launch: a refused call leaves save untouched
+  if (B < 1 || L < 1 || L > kMaxTok || D < 1 || !save || !gram ||
+      (reinterpret_cast<uintptr_t>(save) & 15) != 0 ||
+      (blindno_tok_gram_nchunk(D) > 1 && !gram_partial))
+    return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   const int64_t BL = (int64_t)B * L, BLL = BL * L;
   float4* stt = reinterpret_cast<float4*>(save);
@@ -1019,14 +1068,12 @@ BLINDNO_API int blindno_tok_attn_fwd(const float* X, const float* lw, const floa
   float* Pm = A + BLL;
   float* kap = Pm + BLL;
   float* U = kap + B;
-  if ((reinterpret_cast<uintptr_t>(save) & 15) != 0) return (int)hipErrorInvalidValue;
-  tok_mean_kernel<<<(unsigned)BL, kBlock, 0, st>>>(X, xbar, D);
+  tok_mean_kernel<<<(unsigned)BL, kBlock, 0, st>>>(X, xbar, stt, D);
   const int nch = blindno_tok_gram_nchunk(D);
   const int nb = (L + 3) / 4, nblk = nb * (nb + 1) / 2;
   const size_t lds = (size_t)L * (kGramPts + 1) * sizeof(float);
   float* gdst = nch > 1 ? gram_partial : gram;
-  if (nch > 1 && !gram_partial) return (int)hipErrorInvalidValue;
-  tok_gram_kernel<<<dim3(nch, (nblk + kBlock - 1) / kBlock, B), kBlock, lds, st>>>(X, xbar, gdst, B, L, D);
+  tok_gram_kernel<<<dim3(nch, (nblk + kBlock - 1) / kBlock, B), kBlock, lds, st>>>(X, xbar, stt, gdst, B, L, D);
   int err = (int)hipGetLastError();
   if (err) return err;
   if (nch > 1) {
@@ -1068,12 +1115,12 @@ BLINDNO_API int blindno_tok_attn_bwd(const float* dY, const float* X, const floa
   if (dlw || dlb)
     tok_ln_wgrad_kernel<<<(unsigned)((D + kBlock - 1) / kBlock), kBlock, 0, st>>>(dY, U, dlw, dlb, B, D);
   if (dX) {
-    tok_bwd_dot_kernel<<<(unsigned)BL, kBlock, 0, st>>>(X, xbar, dY, lw, h, gb, L, D);
+    tok_bwd_dot_kernel<<<(unsigned)BL, kBlock, 0, st>>>(X, xbar, stt, dY, lw, h, gb, L, D);
     float2* abv = reinterpret_cast<float2*>(h + BL + B + 2 * BLL + ((BL + B) & 1));
     tok_bwd_rows_kernel<<<dim3(L, B), kRowThreads, 0, st>>>(A, Pm, stt, h, Wk, abv, L, D);
-    tok_bwd_rrow_kernel<<<dim3(L, B), kRowThreads, 0, st>>>(A, Wk, abv, xbar, gb, R, coef, L, D);
+    tok_bwd_rrow_kernel<<<dim3(L, B), kRowThreads, 0, st>>>(A, Wk, abv, xbar, R, coef, L, D);
     tok_bwd_dx_kernel<<<dim3((unsigned)((D + kBlock - 1) / kBlock), (L + kTT - 1) / kTT, B), kBlock, 0,
-                        st>>>(X, xbar, R, coef, lw, dY, dX, L, D);
+                        st>>>(X, xbar, stt, R, coef, lw, dY, gb, dX, L, D);
   }
   return (int)hipGetLastError();
 }

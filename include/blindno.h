@@ -951,5 +951,6 @@ int blindno_project3d_bwd(const float* z, const float* w1, const float* b1, cons
 #include "blindno_unet3d.h"
 #include "blindno_physattn.h"
 #include "blindno_planemlp.h"
+#include "blindno_bagattn_mix.h"
 
 #endif /* BLINDNO_H */

@@ -9,7 +9,7 @@ there is no CPU fallback.  Importing the package registers the hot-path operator
 from . import _lib  # noqa: F401
 from ._lib import BlindnoError, load as load_library  # noqa: F401
 from .fno import FNO1d, FNO2d, FNO3d, MLP, SpectralConv1d, SpectralConv2d, SpectralConv3d  # noqa: F401
-from .nio import (NIOFP, NIOFP2D, NIOFP2D_FNO, NIOFP2D_FNO_attn, NIOFP2D_Trans, NIOFP2D_attn,  # noqa: F401
+from .nio import (NIOFP, NIOFP2D, NIOFP2D_FNO, NIOFP2D_FNO_attn, NIOFP2D_Trans, NIOFP2D_Trans_attn, NIOFP2D_attn,  # noqa: F401
                   NIOFP3D, NIOFP3D_FNO, NIOFP3D_Trans, NIOFP_FNO, NIOFP_schrodinger, draw_bag)
 from .transolver import PhysicsAttention2D, Transolver2D, TransolverBlock2D  # noqa: F401
 from .transolver3d import PhysicsAttention3D, Transolver3D, TransolverBlock3D  # noqa: F401

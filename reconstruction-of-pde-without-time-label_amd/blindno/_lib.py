@@ -302,6 +302,18 @@ SIGNATURES_PLANEMLP = {
     "blindno_plane_mlp_bwd": "pl" + "pl" + "ppppp" + "pp" + "p" + "pl" + "pppppp" + "iiiii" + "s",
 }
 
+# include/blindno_bagattn_mix.h: the multiplicity-weighted bag token attention of NIOFP2D_Trans_attn
+# on a deduplicated bag (csrc/bagattn_mix.hip)
+SIGNATURES_BAGATTN_MIX = {
+    "blindno_bagattn_mix_ok": "iiii",
+    "blindno_bagattn_mix_nchunk": "i",
+    "blindno_bagattn_mix_bwd_nchunk": "i",
+    "blindno_bagattn_mix_fwd_scratch_floats": "iii",
+    "blindno_bagattn_mix_fwd": "ppppp" + "pppp" + "iiiii" + "s",
+    "blindno_bagattn_mix_bwd_scratch_floats": "iii",
+    "blindno_bagattn_mix_bwd": "ppppppp" + "ppp" + "iiiii" + "s",
+}
+
 # entry points returning int64_t (byte counts) instead of an error code / int count
 RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))} | \
     {n for n in SIGNATURES_GPE3D if n.endswith(("_doubles", "_launches"))} | \
@@ -313,7 +325,8 @@ RET64 = {n for n in SIGNATURES if n.endswith(("_bytes", "_floats"))} | \
     {n for n in SIGNATURES_BAG3D if n.endswith("_floats")} | \
     {n for n in SIGNATURES_NIOATTN if n.endswith("_floats")} | \
     {n for n in SIGNATURES_PHYSATTN if n.endswith("_floats")} | \
-    {n for n in SIGNATURES_PLANEMLP if n.endswith("_floats")}
+    {n for n in SIGNATURES_PLANEMLP if n.endswith("_floats")} | \
+    {n for n in SIGNATURES_BAGATTN_MIX if n.endswith("_floats")}
 
 _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_int64, "f": ctypes.c_float,
        "d": ctypes.c_double, "s": ctypes.c_void_p}
@@ -342,7 +355,8 @@ def load():
                           **SIGNATURES_BAG3D, **SIGNATURES_GPE3D, **SIGNATURES_FPE_ERR,
                           **SIGNATURES_GPE3D_ERR, **SIGNATURES_GPE2D_ERR,
                           **SIGNATURES_NIOATTN, **SIGNATURES_UNET3D,
-                          **SIGNATURES_PHYSATTN, **SIGNATURES_PLANEMLP}.items():
+                          **SIGNATURES_PHYSATTN, **SIGNATURES_PLANEMLP,
+                          **SIGNATURES_BAGATTN_MIX}.items():
             fn = getattr(lib, name)
             fn.argtypes = [_CT[c] for c in sig]
             fn.restype = ctypes.c_int64 if name in RET64 else ctypes.c_int
@@ -357,7 +371,7 @@ def exported_symbols():
             list(SIGNATURES_BAG3D) + list(SIGNATURES_GPE3D) + list(SIGNATURES_FPE_ERR) +
             list(SIGNATURES_GPE3D_ERR) + list(SIGNATURES_GPE2D_ERR) + list(SIGNATURES_NIOATTN) +
             list(SIGNATURES_UNET3D) + list(SIGNATURES_PHYSATTN) + list(SIGNATURES_PLANEMLP) +
-            ["blindno_error_string"])
+            list(SIGNATURES_BAGATTN_MIX) + ["blindno_error_string"])
 
 
 def stream_ptr(device=None):

@@ -1,6 +1,6 @@
 """Snapshot-bag (time-label-free) models: NIOFP2D_FNO, NIOFP_FNO, NIOFP2D, NIOFP2D_attn,
-NIOFP2D_Trans, NIOFP, NIOFP_schrodinger, NIOFP3D -- drop-in for the reference's NIOModules -- and
-NIOFP3D_FNO and
+NIOFP2D_Trans, NIOFP2D_Trans_attn, NIOFP, NIOFP_schrodinger, NIOFP3D -- drop-in for the reference's
+NIOModules -- and NIOFP3D_FNO and
 NIOFP3D_Trans, the project's own 3D FNO-NIO and 3D Transolver-NIO (the reference has no such
 classes).
 
@@ -452,6 +452,74 @@ class NIOFP2D_Trans(nn.Module):
         u = self.trans_input.forward_planes(inp)                      # (B L, 1, n, n)
         h = _bag_mean_2d(self, u, grid, B, L, n, n, lw)
         return _run_heads(self, h)
+
+
+class NIOFP2D_Trans_attn(nn.Module):
+    """Transolver snapshot encoder + bag token attention + FNO heads, 2d_FPE/NIOModules.py:169-296
+    and 2d_Non_conservative_FPE/NIOModules.py:168-295 (both name the heads fno_drift /
+    fno_diffusion).
+
+    Every drawn snapshot goes through ``trans_input`` as in NIOFP2D_Trans; the tokens [gx, gy,
+    u_1..u_L] then attend to each other (softmax(X X^T / sqrt(nx ny)) X) and the token outputs are
+    fused with fc0 = Linear(3, width) read through ``.data``: the grid tokens' outputs with
+    fc0.weight[:, 0] and [:, 1], the snapshot tokens' mean output with [:, 2].
+
+    The reference assigns ``self.fc0`` twice: the second Linear(3, width) is created after the
+    heads (it draws from the RNG there) and keeps the first one's slot in the module order.  The
+    construction below does the same, so a seeded construction gives the reference's weights.
+
+    The draw is with replacement.  The Transolver runs once per distinct snapshot, and
+    ops.BagAttnMixFn runs the attention on the distinct tokens with their multiplicities: a
+    duplicate's row and column of the attention matrix are copies of its original's, so the
+    softmax normaliser counts each distinct token multiplicity times and nothing of the size of
+    the drawn bag is formed."""
+
+    GRID = NIOFP2D_Trans.GRID
+
+    def __init__(self, input_dimensions_trunk, n_hidden_layers, neurons, n_basis, fno_layers,
+                 width, modes, output_dim, nx, ny,
+                 heads: Sequence[str] = ("fno_drift", "fno_diffusion"), branch_last_kernel=(2, 1)):
+        super().__init__()
+        output_dimensions = n_basis
+        self.fno_layers = fno_layers
+        self.branch = Encoder2D(output_dimensions, last_kernel=branch_last_kernel)
+        self.fc0 = nn.Linear(3, width)
+        self.trans_input = Transolver2D(space_dim=2, n_layers=3, n_hidden=32, dropout=0.0, n_head=4,
+                                        Time_Input=False, mlp_ratio=1, fun_dim=1, out_dim=1,
+                                        slice_num=16, ref=8, unified_pos=False, H=self.GRID,
+                                        W=self.GRID)
+        self._heads = tuple(heads)
+        for name in self._heads:
+            setattr(self, name, FNO2d(modes=modes, width=width, n_layers=self.fno_layers,
+                                      input_dim=width, output_dim=1))
+        self.fc0 = nn.Linear(3, width)      # the reference's second assignment: drawn last
+        self.nx = nx
+        self.ny = ny
+
+    unused_prefixes = NIOFP2D_Trans.unused_prefixes
+
+    def forward(self, x, grid, bag_idx=None):
+        """x (B, T, 61, 61), grid (61, 61, 2) -> (B, 61, 61, 2).  ``bag_idx`` (a host index list)
+        overrides the train-mode draw (draw_bag: with replacement); eval mode uses all T."""
+        ops.require_device(x, grid)
+        n = self.GRID
+        if x.dim() != 4 or tuple(x.shape[2:]) != (n, n) or tuple(grid.shape) != (n, n, 2):
+            raise ValueError(f"NIOFP2D_Trans_attn: the reference's Transolver is built for a {n} x {n} "
+                             f"grid; got x {tuple(x.shape)} and grid {tuple(grid.shape)}")
+        if isinstance(bag_idx, tuple) or (torch.is_tensor(bag_idx) and bag_idx.is_cuda):
+            raise ValueError("NIOFP2D_Trans_attn: bag_idx must be a host index list (the attention "
+                             "needs the number of draws; graph capture is not supported)")
+        if bag_idx is None and self.training:
+            _, bag_idx = draw_bag(x.shape[1])
+        drawn = x.shape[1] if bag_idx is None else len(bag_idx)
+        x, U, lw = _select(self, x, bag_idx, dedup=True)
+        B = x.shape[0]
+        g = grid.permute(2, 0, 1).unsqueeze(0).expand(B * U, 2, n, n)
+        inp = torch.cat((x.reshape(B * U, 1, n, n), g), dim=1)        # [rho, gx, gy] planes
+        u = self.trans_input.forward_planes(inp)                      # (B U, 1, n, n)
+        h = ops.BagAttnMixFn.apply(u.reshape(B, U, n * n), grid.reshape(n * n, 2),
+                                   self.fc0.weight.data, self.fc0.bias.data, lw, drawn)
+        return _run_heads(self, h.view(B, n, n, -1))
 
 
 class NIOFP3D(nn.Module):

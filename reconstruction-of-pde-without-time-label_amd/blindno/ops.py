@@ -2380,6 +2380,63 @@ class BagAttnFn(torch.autograd.Function):
         return (du if ctx.needs_input_grad[0] else None), ggrid, None, None
 
 
+class BagAttnMixFn(torch.autograd.Function):
+    """Multiplicity-weighted token self-attention + fc0 fusion of NIOFP2D_Trans_attn
+    (2d_FPE/NIOModules.py:241-278) on a deduplicated bag (csrc/bagattn_mix.hip,
+    include/blindno_bagattn_mix.h): u (B, U, S) the encoded DISTINCT snapshots, grid (S, 2) ->
+    (B, S, width).  ``lw`` (U) holds multiplicity / L of each distinct snapshot and ``L`` the number
+    of draws; without them every snapshot counts once (L = U).  ``w``/``bias`` are
+    ``fc0.weight.data``/``.bias.data`` (fc0 = Linear(3, width), never trained): the grid tokens'
+    outputs are fused with w[:, 0] and w[:, 1], the snapshot tokens' with w[:, 2] / L.  Gradients
+    for u (per distinct snapshot: the sum over its duplicates) and for the grid."""
+
+    @staticmethod
+    def forward(ctx, u, grid, w, bias, lw=None, L=None):
+        require_device(u, grid, w, bias, lw)
+        u, grid, lw = _c(u), _c(grid), _c(lw)
+        w, bias = _c(w.detach()), _c(bias.detach())
+        if u.dim() != 3:
+            raise BlindnoError(f"bag attention: u must be (B, U, S), got {tuple(u.shape)}")
+        B, U, S = u.shape
+        V = U + 2
+        if V > 256:
+            raise BlindnoError(f"bag attention supports at most 256 tokens (U + 2), got {V}")
+        if tuple(grid.shape) != (S, 2) or w.dim() != 2 or w.shape[1] != 3 or bias.numel() != w.shape[0]:
+            raise BlindnoError(f"bag attention: grid {tuple(grid.shape)} / fc0 {tuple(w.shape)}, "
+                               f"{tuple(bias.shape)} do not match S={S} and Linear(3, width)")
+        if lw is not None:
+            if L is None:
+                raise BlindnoError("bag attention: lw (multiplicity / L) needs the number of draws L")
+            if tuple(lw.shape) != (U,) or int(L) < U:
+                raise BlindnoError(f"bag attention: lw {tuple(lw.shape)} / L={L} do not match U={U}")
+        Ld = U if lw is None else int(L)
+        width = w.shape[0]
+        if not query("blindno_bagattn_mix_ok", B, U, S, width):
+            raise BlindnoError(f"bag attention: unsupported shape B={B} U={U} S={S} width={width}")
+        scratch = _empty(query("blindno_bagattn_mix_fwd_scratch_floats", B, U, S), like=u)
+        P = _empty(B, V, V, like=u)
+        r = _empty(B, 3, V, like=u)
+        y = _empty(B, S, width, like=u)
+        call("blindno_bagattn_mix_fwd", ptr(grid), ptr(u), ptr(w), ptr(bias), ptr(lw), ptr(scratch),
+             ptr(P), ptr(r), ptr(y), B, U, S, width, Ld, stream_ptr())
+        ctx.save_for_backward(u, grid, w, P, r)
+        ctx.lw, ctx.L = lw, Ld
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        u, grid, w, P, r = ctx.saved_tensors
+        B, U, S = u.shape
+        gy = _c(gy)
+        scratch = _empty(query("blindno_bagattn_mix_bwd_scratch_floats", B, U, S), like=gy)
+        du = _empty(B, U, S, like=gy)
+        dgt = _empty(B, 2, S, like=gy) if ctx.needs_input_grad[1] else None
+        call("blindno_bagattn_mix_bwd", ptr(grid), ptr(u), ptr(gy), ptr(w), ptr(ctx.lw), ptr(P), ptr(r),
+             ptr(scratch), ptr(du), ptr(dgt), B, U, S, w.shape[0], ctx.L, stream_ptr())
+        ggrid = dgt.sum(0).t() if dgt is not None else None
+        return (du if ctx.needs_input_grad[0] else None), ggrid, None, None, None, None
+
+
 class NIOAttnFn(torch.autograd.Function):
     """DeepONet combiner + bag token attention + fixed-weight fusion of NIOFP2D_attn
     (2d_FPE/NIOModules.py:459-495) in coefficient space (csrc/nioattn.hip, include/blindno_nioattn.h):

@@ -170,8 +170,20 @@ def _own_experiments(model: str = "fno"):
     datagen.fpe_3d_dataset files -- the 2D UNet entry's lr, batch and eval period, an eager step,
     one process only, results_3d_FPE_unet/.  ``model="trans"``: 2d_FPE with NIOFP2D_Trans(2, 3, 100,
     25, 3, 12, 32, 2) (2d_FPE/NIOModules.py:85-166; 61 x 61 datasets only) -- the 2d_FPE UNet entry's
-    lr, batch and eval period, an eager step, one process only, results_2d_FPE_trans/."""
+    lr, batch and eval period, an eager step, one process only, results_2d_FPE_trans/.
+    ``model="trans_attn"``: the same entry with NIOFP2D_Trans_attn(2, 3, 100, 25, 3, 12, 32, 2, n, n)
+    (2d_FPE/NIOModules.py:169-296), results_2d_FPE_trans_attn/."""
     all4 = ("train_losses", "test_losses", "test_losses_drift", "test_losses_diffusion")
+    if model == "trans_attn":
+        from . import data, nio
+        from .encoders import Encoder2D
+        return {
+            "2d_FPE": Experiment("2d_FPE", 2, data.TrajectoryDataset2D,
+                                 lambda n, dev: nio.NIOFP2D_Trans_attn(
+                                     2, 3, 100, 25, 3, 12, 32, 2, n, n,
+                                     branch_last_kernel=Encoder2D.kernel_for_grid(n)),
+                                 5e-4, 4, 5, "results_2d_FPE_trans_attn", True, all4, eager=True),
+        }
     if model == "trans":
         from . import data, nio
         from .encoders import Encoder2D
@@ -376,9 +388,10 @@ class Trainer:
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--experiment", choices=sorted(_experiments()), default="2d_FPE")
-    ap.add_argument("--model", choices=["fno", "unet", "nio", "trans"], default="fno",
+    ap.add_argument("--model", choices=["fno", "unet", "nio", "trans", "trans_attn"], default="fno",
                     help="fno: train_fno*.py (NIO-FNO); unet: train_unet*.py (attention UNet); "
-                         "nio: train_nio*.py (DeepONet-branch NIO); trans: NIOFP2D_Trans (2d_FPE)")
+                         "nio: train_nio*.py (DeepONet-branch NIO); trans: NIOFP2D_Trans (2d_FPE); "
+                         "trans_attn: NIOFP2D_Trans_attn (2d_FPE)")
     ap.add_argument("--data", required=True, help="the experiment's dataset file (npz, or the GPE .npy dict)")
     ap.add_argument("--outdir", default=None, help="result directory (default: the reference's)")
     ap.add_argument("--epochs", type=int, default=400)
@@ -393,7 +406,7 @@ def main(argv=None):
     exps = experiments_for(a.model)
     if a.experiment not in exps:
         ap.error(f"--experiment {a.experiment} has no --model {a.model} configuration "
-                 f"(it has: {', '.join(m for m in ('fno', 'unet', 'nio', 'trans') if a.experiment in experiments_for(m))})")
+                 f"(it has: {', '.join(m for m in ('fno', 'unet', 'nio', 'trans', 'trans_attn') if a.experiment in experiments_for(m))})")
     exp = exps[a.experiment]
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))

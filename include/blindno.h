@@ -51,7 +51,8 @@ int blindno_lift_fwd(const float* in, const float* w0, const float* b0, float* x
 
 /* Backward of the lift: optional d_in (may be NULL) and per-chunk partial sums of
  * dW0 (C*Cin) then db0 (C) into partial[nchunk][C*Cin + C], nchunk =
- * blindno_lift_bwd_nchunk(Bn, N1, N2). */
+ * blindno_lift_bwd_nchunk(Bn, N1, N2).  N1 > P1, N2 > P2, a wrong nchunk or C*Cin + C > 1024 is
+ * refused with hipErrorInvalidValue before anything is launched (d_in stays untouched too). */
 int blindno_lift_bwd(const float* dx0, const float* in, const float* w0, float* d_in,
                      float* partial, int nchunk,
                      int Bn, int N1, int N2, int Cin, int C, int P1, int P2,

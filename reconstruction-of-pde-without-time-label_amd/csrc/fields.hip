@@ -1049,10 +1049,13 @@ BLINDNO_API int blindno_lift_bwd_bag_mix_g(const float* dx0, const float* in, co
                                            int m2, const float* ubar, const float* grid,
                                            const float* bw, const float* bb, float invL,
                                            float invLb, void* stream) {
-  if (G < 1 || Bn % G) return (int)hipErrorInvalidValue;
+  // every refusal comes before the first launch: a refused call leaves all its outputs alone
+  if (G < 1 || Bn % G || N1 > P1 || N2 > P2) return (int)hipErrorInvalidValue;
   const BagIn bi{ubar, grid, bw, bb, invL, invLb};
   if (ubar && (!grid || !bw || !bb)) return (int)hipErrorInvalidValue;
   const int Bg = Bn / G;
+  if (partial && (nchunk != blindno_lift_bwd_nchunk(Bg, N1, N2) || C * Cin + C > PPT * kBlock))
+    return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   const bool wide_in = d_in && Cin == 12 && C <= kLiftMaxC && G <= kLiftMaxG &&
                        (int64_t)Bn * C * P1 * P2 < INT32_MAX &&

@@ -3,7 +3,7 @@
  * Included by blindno.h (include that one); same conventions: every entry returns a hipError_t
  * code as int (0 = success) unless it is a size query, pointers are device pointers, the last
  * argument is the stream.  The Python binding keeps these entries in
- * blindno._lib.SIGNATURES_BAG3D, one table per header.
+ * blindno._lib.ABI["blindno_bag3d.h"].
  */
 #ifndef BLINDNO_BAG3D_H
 #define BLINDNO_BAG3D_H

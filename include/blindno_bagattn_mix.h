@@ -3,7 +3,7 @@
  * Included by blindno.h (include that one); same conventions: every entry returns a hipError_t
  * code as int (0 = success) unless it is a query, pointers are device pointers, the last
  * argument is the stream, nothing is allocated and nothing synchronises inside.  The Python
- * binding keeps these entries in blindno._lib.SIGNATURES_BAGATTN_MIX, one table per header.
+ * binding keeps these entries in blindno._lib.ABI["blindno_bagattn_mix.h"].
  */
 #ifndef BLINDNO_BAGATTN_MIX_H
 #define BLINDNO_BAGATTN_MIX_H

@@ -4,7 +4,7 @@
  * Included by blindno.h (include that one); same conventions: every entry returns a hipError_t
  * code as int (0 = success) unless it is a size query, pointers are device pointers, the last
  * argument is the stream, nothing is allocated and nothing synchronises inside.  The Python
- * binding keeps these entries in blindno._lib.SIGNATURES_GPE2D, one table per header.
+ * binding keeps these entries in blindno._lib.ABI["blindno_gpe2d.h"].
  */
 #ifndef BLINDNO_GPE2D_H
 #define BLINDNO_GPE2D_H

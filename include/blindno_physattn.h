@@ -4,7 +4,7 @@
  * Included by blindno.h (include that one); same conventions: every entry returns a hipError_t
  * code as int (0 = success) unless it is a size query, pointers are device pointers, the last
  * argument is the stream, nothing is allocated and nothing synchronises inside.  The Python
- * binding keeps these entries in blindno._lib.SIGNATURES_PHYSATTN, one table per header.
+ * binding keeps these entries in blindno._lib.ABI["blindno_physattn.h"].
  */
 #ifndef BLINDNO_PHYSATTN_H
 #define BLINDNO_PHYSATTN_H

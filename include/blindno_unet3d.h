@@ -7,7 +7,7 @@
  * a fixed-order tree or per-chunk partials summed in chunk order by blindno_reduce_partials: no
  * float atomics, a second call is bit-identical.  Offsets are 64-bit; one (n, c) volume must
  * stay below 2^31 voxels.  The Python binding keeps these entries in
- * blindno._lib.SIGNATURES_UNET3D.
+ * blindno._lib.ABI["blindno_unet3d.h"].
  *
  * The rest of the 3D UNet runs on entries that take a 3D field unchanged: blindno_conv3d_* (the
  * 3x3x3 and 1x1x1 convolutions), blindno_cnx_pw_* and blindno_bn_act_* with HW = D H W, and

@@ -1,43 +1,18 @@
-"""The record-free Fokker-Planck error path without a GPU: the binding of include/blindno_fpe_err.h,
-the launch plan and budgets of blindno.fpe.propagate_error_many, the 3d_FPE kind of blindno.evaluate
+"""The record-free Fokker-Planck error path without a GPU: the scratch query of
+include/blindno_fpe_err.h, the launch plan and budgets of blindno.fpe.propagate_error_many, the 3d_FPE kind of blindno.evaluate
 against data.TrajectoryDataset3D, and the 3d_FPE trainer experiment's configuration.
 """
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
 from fpe3d_ref import initial, make_sim
 
 
-def test_fpe_err_symbols_declared_and_bound():
-    """include/blindno_fpe_err.h (included by blindno.h) <=> _lib.SIGNATURES_FPE_ERR <=> the library."""
-    import blindno
+def test_fpe_err_scratch_query_without_a_device():
+    """The host-only size query: the density, two iterates and two partials per tile; -1 when
+    refused."""
     from blindno import _lib
-    assert '#include "blindno_fpe_err.h"' in open(os.path.join(ROOT, "include", "blindno.h")).read()
-    hdr = open(os.path.join(ROOT, "include", "blindno_fpe_err.h")).read()
-    decl = sorted(set(re.findall(r"^(?:int|int64_t|const char\*)\s+(blindno_\w+)\(", hdr, re.M)))
-    assert decl == sorted(_lib.SIGNATURES_FPE_ERR) == ["blindno_fp_error_nd", "blindno_fp_error_nd_scratch_doubles"]
-    others = (set(_lib.SIGNATURES) | set(_lib.SIGNATURES_CONV3D) | set(_lib.SIGNATURES_FPE) |
-              set(_lib.SIGNATURES_GPE2D) | set(_lib.SIGNATURES_BAG3D) | set(_lib.SIGNATURES_GPE3D))
-    assert not set(_lib.SIGNATURES_FPE_ERR) & others
-    lib = blindno.load_library()
-    kinds = {"p": r"\*", "i": r"^int\b", "d": r"^double\b", "s": r"^blindno_stream_t\b"}
-    for s in decl:
-        assert hasattr(lib, s) and s in _lib.exported_symbols(), s
-        m = re.search(r"\b(?:int|int64_t)\s+" + s + r"\s*\(([^;]*)\)\s*;", hdr)
-        args = [a.strip() for a in m.group(1).split(",") if a.strip()]
-        sig = _lib.SIGNATURES_FPE_ERR[s]
-        assert len(args) == len(sig) == len(getattr(lib, s).argtypes), (s, args)
-        for a, c in zip(args, sig):                               # pointer / int / double / stream, in order
-            assert re.search(kinds[c], a) and (c == "p") == ("*" in a), (s, a, c)
-    # the propagator's argument list with `group` after B, and err in place of out
-    assert _lib.SIGNATURES_FPE_ERR["blindno_fp_error_nd"] == _lib.SIGNATURES_FPE["blindno_fp_propagate_nd"].replace(
-        "ppppi", "ppppii", 1)
-    assert "blindno_fp_error_nd_scratch_doubles" in _lib.RET64
-    # the host-only size query: the density, two iterates and two partials per tile; -1 when refused
     q = lambda *a: _lib.query("blindno_fp_error_nd_scratch_doubles", *a)   # noqa: E731
     assert q(6, 40, 40, 40) == 3 * 6 * 64000 + 2 * 6 * 250
     assert q(1, 5, 4, 3) == 3 * 60 + 2 and q(2, 7, 6, 7) == 2 * (3 * 294 + 2 * 2)

@@ -1,12 +1,11 @@
-"""3D Fokker-Planck rates, the (7, N) coefficient table of blindno_fp_propagate_nd, its binding, the
-launch budget of the grid-resident path and TrajectoryDataset3D (no GPU needed).
+"""3D Fokker-Planck rates, the (7, N) coefficient table of blindno_fp_propagate_nd, its scratch
+query, the launch budget of the grid-resident path and TrajectoryDataset3D (no GPU needed).
 
 PARITY UNPINNED as in tests/test_fpe.py (fplanck is absent, and the reference has no 3D generator at
 all): the checker is tests/fpe3d_ref.py's independent sparse assembly of the same master equation
 and its physical invariants (mass conservation, the Boltzmann stationary state).
 """
 import os
-import re
 
 import numpy as np
 import pytest
@@ -75,22 +74,9 @@ def test_potential_from_data_on_a_3d_grid():
     assert np.allclose(sim2.potential_values, sim.potential_values, rtol=1e-12, atol=0)
 
 
-def test_fpe_symbols_declared_and_bound():
-    """include/blindno_fpe.h (included by blindno.h) <=> _lib.SIGNATURES_FPE <=> the library."""
-    import blindno
+def test_fpe_scratch_query_without_a_device():
+    """The host-only size query: two iterates per cell, int64, -1 for a refused grid."""
     from blindno import _lib
-    assert '#include "blindno_fpe.h"' in open(os.path.join(ROOT, "include", "blindno.h")).read()
-    hdr = open(os.path.join(ROOT, "include", "blindno_fpe.h")).read()
-    decl = sorted(set(re.findall(r"^(?:int|int64_t|const char\*)\s+(blindno_\w+)\(", hdr, re.M)))
-    assert decl == sorted(_lib.SIGNATURES_FPE) and len(decl) == 2
-    assert not set(_lib.SIGNATURES_FPE) & (set(_lib.SIGNATURES) | set(_lib.SIGNATURES_CONV3D))
-    lib = blindno.load_library()
-    for s in decl:
-        assert hasattr(lib, s) and s in _lib.exported_symbols(), s
-        m = re.search(r"\b(?:int|int64_t)\s+" + s + r"\s*\(([^;]*)\)\s*;", hdr)
-        nargs = len([a for a in m.group(1).split(",") if a.strip()])
-        assert nargs == len(_lib.SIGNATURES_FPE[s]) == len(getattr(lib, s).argtypes), (s, nargs)
-    # the host-only size query: two iterates per cell, int64, -1 for a refused grid
     q = lambda *a: _lib.query("blindno_fp_propagate_nd_scratch_doubles", *a)   # noqa: E731
     assert q(8, 40, 40, 40) == 2 * 8 * 64000
     assert q(600, 2048, 2048, 1) == 2 * 600 * 2048 * 2048 > 2 ** 32

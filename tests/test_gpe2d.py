@@ -1,4 +1,4 @@
-"""2D GPE: the binding of include/blindno_gpe2d.h, internal checks on the numpy reference
+"""2D GPE: the host-only queries of include/blindno_gpe2d.h, internal checks on the numpy reference
 tests/gpe2d_ref.py that the GPU tests compare against, the generator's draws and keys, the
 request guards of solve_batch_2d and the 2d_GPE experiment entry (no GPU needed).
 
@@ -7,7 +7,6 @@ it): the checker is gpe2d_ref, tied to the reference's own numbers through its r
 1D oracle (pinned by tests/golden/gpe_solve_*.npz) when nothing depends on y.
 """
 import os
-import re
 
 import numpy as np
 import pytest
@@ -28,24 +27,9 @@ def _problem(nx, ny, seed=0):
     return x, y, V, psi0
 
 
-def test_gpe2d_symbols_declared_and_bound():
-    """include/blindno_gpe2d.h (included by blindno.h) <=> _lib.SIGNATURES_GPE2D <=> the library."""
-    import blindno
+def test_gpe2d_queries_without_a_device():
+    """The host-only queries: one working field, int64; -1 for a refused grid."""
     from blindno import _lib
-    assert '#include "blindno_gpe2d.h"' in open(os.path.join(ROOT, "include", "blindno.h")).read()
-    hdr = open(os.path.join(ROOT, "include", "blindno_gpe2d.h")).read()
-    decl = sorted(set(re.findall(r"^(?:int|int64_t|const char\*)\s+(blindno_\w+)\(", hdr, re.M)))
-    assert decl == sorted(_lib.SIGNATURES_GPE2D) and len(decl) == 4
-    assert {"blindno_gpe2d_solve", "blindno_trapz2_frames"} <= set(decl)
-    assert not set(_lib.SIGNATURES_GPE2D) & (set(_lib.SIGNATURES) | set(_lib.SIGNATURES_CONV3D) |
-                                             set(_lib.SIGNATURES_FPE))
-    lib = blindno.load_library()
-    for s in decl:
-        assert hasattr(lib, s) and s in _lib.exported_symbols(), s
-        m = re.search(r"\b(?:int|int64_t)\s+" + s + r"\s*\(([^;]*)\)\s*;", hdr)
-        nargs = len([a for a in m.group(1).split(",") if a.strip()])
-        assert nargs == len(_lib.SIGNATURES_GPE2D[s]) == len(getattr(lib, s).argtypes), (s, nargs)
-    # the host-only queries: one working field, int64; -1 for a refused grid
     q = lambda *a: _lib.query("blindno_gpe2d_scratch_doubles", *a)   # noqa: E731
     assert q(16, 256, 256) == 2 * 16 * 256 * 256
     assert q(4096, 1024, 1024) == 2 * 4096 * 1024 * 1024 > 2 ** 32

@@ -1,5 +1,5 @@
-"""The record-free 2D GPE error path without a GPU: the binding of include/blindno_gpe2d_err.h, its
-two host-only queries, and the request guards of gpe.solve_error_batch_2d.
+"""The record-free 2D GPE error path without a GPU: the two host-only queries of
+include/blindno_gpe2d_err.h, and the request guards of gpe.solve_error_batch_2d.
 """
 import os
 import re
@@ -18,50 +18,24 @@ def _tile():
     return int(m.group(1))
 
 
-def test_gpe2d_err_symbols_declared_and_bound():
-    """include/blindno_gpe2d_err.h (included by blindno.h) <=> _lib.SIGNATURES_GPE2D_ERR <=> the library."""
-    import blindno
-    from blindno import _lib
-    assert '#include "blindno_gpe2d_err.h"' in open(os.path.join(ROOT, "include", "blindno.h")).read()
-    hdr = open(HDR).read()
-    decl = sorted(set(re.findall(r"^(?:int|int64_t|const char\*)\s+(blindno_\w+)\(", hdr, re.M)))
-    assert decl == sorted(_lib.SIGNATURES_GPE2D_ERR) == NAMES
-    lib = blindno.load_library()
-    kinds = {"p": r"\*", "i": r"^int\b", "d": r"^double\b", "s": r"^blindno_stream_t\b"}
-    for s in decl:
-        assert hasattr(lib, s) and s in _lib.exported_symbols(), s
-        m = re.search(r"\b(?:int|int64_t)\s+" + s + r"\s*\(([^;]*)\)\s*;", hdr)
-        args = [a.strip() for a in m.group(1).split(",") if a.strip()]
-        sig = _lib.SIGNATURES_GPE2D_ERR[s]
-        assert len(args) == len(sig) == len(getattr(lib, s).argtypes), (s, args)
-        for a, c in zip(args, sig):                               # pointer / int / double / stream, in order
-            assert re.search(kinds[c], a) and (c == "p") == ("*" in a), (s, a, c)
-    assert {"blindno_gpe2d_error_scratch_doubles", "blindno_gpe2d_error_launches"} <= _lib.RET64
-    assert "blindno_gpe2d_error" not in _lib.RET64
-    # the solver's arguments in its order: x, y after kappa; group, err in place of the four outputs
-    assert _lib.SIGNATURES_GPE2D_ERR["blindno_gpe2d_error"] == \
-        "pppp" + "pp" + "ddd" + "iii" + "i" + "p" + "p" + "iiii" + "s"
-    assert _lib.SIGNATURES_GPE2D["blindno_gpe2d_solve"] == "pppp" + "ddd" + "iii" + "pipp" + "p" + "iiii" + "s"
-
-
 def test_gpe2d_header_still_declares_four_entries():
     """The new entries live in their own header: blindno_gpe2d.h keeps its four."""
     from blindno import _lib
     hdr = open(os.path.join(ROOT, "include", "blindno_gpe2d.h")).read()
     decl = sorted(set(re.findall(r"^(?:int|int64_t|const char\*)\s+(blindno_\w+)\(", hdr, re.M)))
-    assert decl == sorted(_lib.SIGNATURES_GPE2D) and len(decl) == 4
+    assert decl == sorted(_lib.ABI["blindno_gpe2d.h"]) and len(decl) == 4
     assert not re.findall(r"blindno_gpe2d_error", hdr)
 
 
 def test_gpe2d_err_table_is_disjoint_from_every_other_table():
     from blindno import _lib
-    tables = {k: v for k, v in vars(_lib).items() if k.startswith("SIGNATURES") and isinstance(v, dict)}
-    assert "SIGNATURES_GPE2D_ERR" in tables and len(tables) >= 9
-    for k, v in tables.items():
-        if k != "SIGNATURES_GPE2D_ERR":
-            assert not set(v) & set(_lib.SIGNATURES_GPE2D_ERR), k
+    own = _lib.ABI["blindno_gpe2d_err.h"]
+    assert sorted(own) == NAMES and len(_lib.ABI) >= 9
+    for k, v in _lib.ABI.items():
+        if k != "blindno_gpe2d_err.h":
+            assert not set(v) & set(own), k
     assert len(_lib.exported_symbols()) == len(set(_lib.exported_symbols()))
-    assert set(_lib.SIGNATURES_GPE2D_ERR) <= set(_lib.exported_symbols())
+    assert set(own) <= set(_lib.exported_symbols())
 
 
 def test_tile_macro_is_a_power_of_two_in_range():

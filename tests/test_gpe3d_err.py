@@ -1,5 +1,5 @@
-"""The record-free 3D GPE error path without a GPU: the binding of include/blindno_gpe3d_err.h, its
-two host-only queries, gpe.time_averaged_L2_error_from_sums against the numpy checker, and the
+"""The record-free 3D GPE error path without a GPU: the two host-only queries of
+include/blindno_gpe3d_err.h, gpe.time_averaged_L2_error_from_sums against the numpy checker, and the
 request guards of gpe.solve_error_batch_3d.
 """
 import os
@@ -21,41 +21,13 @@ def _tile():
     return int(m.group(1))
 
 
-def test_gpe3d_err_symbols_declared_and_bound():
-    """include/blindno_gpe3d_err.h (included by blindno.h) <=> _lib.SIGNATURES_GPE3D_ERR <=> the library."""
-    import blindno
-    from blindno import _lib
-    assert '#include "blindno_gpe3d_err.h"' in open(os.path.join(ROOT, "include", "blindno.h")).read()
-    hdr = open(HDR).read()
-    decl = sorted(set(re.findall(r"^(?:int|int64_t|const char\*)\s+(blindno_\w+)\(", hdr, re.M)))
-    assert decl == sorted(_lib.SIGNATURES_GPE3D_ERR) == NAMES
-    lib = blindno.load_library()
-    kinds = {"p": r"\*", "i": r"^int\b", "d": r"^double\b", "s": r"^blindno_stream_t\b"}
-    for s in decl:
-        assert hasattr(lib, s) and s in _lib.exported_symbols(), s
-        m = re.search(r"\b(?:int|int64_t)\s+" + s + r"\s*\(([^;]*)\)\s*;", hdr)
-        args = [a.strip() for a in m.group(1).split(",") if a.strip()]
-        sig = _lib.SIGNATURES_GPE3D_ERR[s]
-        assert len(args) == len(sig) == len(getattr(lib, s).argtypes), (s, args)
-        for a, c in zip(args, sig):                               # pointer / int / double / stream, in order
-            assert re.search(kinds[c], a) and (c == "p") == ("*" in a), (s, a, c)
-    assert {"blindno_gpe3d_error_scratch_doubles", "blindno_gpe3d_error_launches"} <= _lib.RET64
-    assert "blindno_gpe3d_error" not in _lib.RET64
-    # the solver's arguments in its order: x, y, z after kappa; group, err in place of the four outputs
-    assert _lib.SIGNATURES_GPE3D_ERR["blindno_gpe3d_error"] == \
-        "pppp" + "ppp" + "dddd" + "iii" + "i" + "p" + "p" + "iiiii" + "s"
-    assert _lib.SIGNATURES_GPE3D["blindno_gpe3d_solve"] == "pppp" + "dddd" + "iii" + "pipp" + "p" + "iiiii" + "s"
-    # the new header leaves blindno_gpe3d.h's four entries alone
-    assert not re.findall(r"blindno_gpe3d_error", open(os.path.join(ROOT, "include", "blindno_gpe3d.h")).read())
-
-
 def test_gpe3d_err_table_is_disjoint_from_every_other_table():
     from blindno import _lib
-    tables = {k: v for k, v in vars(_lib).items() if k.startswith("SIGNATURES") and isinstance(v, dict)}
-    assert "SIGNATURES_GPE3D_ERR" in tables and len(tables) >= 8
-    for k, v in tables.items():
-        if k != "SIGNATURES_GPE3D_ERR":
-            assert not set(v) & set(_lib.SIGNATURES_GPE3D_ERR), k
+    own = _lib.ABI["blindno_gpe3d_err.h"]
+    assert sorted(own) == NAMES and len(_lib.ABI) >= 8
+    for k, v in _lib.ABI.items():
+        if k != "blindno_gpe3d_err.h":
+            assert not set(v) & set(own), k
     assert len(_lib.exported_symbols()) == len(set(_lib.exported_symbols()))
 
 

@@ -1,6 +1,6 @@
 """NIOFP3D_FNO without a GPU: the float64 restatement (tests/nio3d_fno_ref.py) pinned to the golden
 run of the same composition in the reference's own fp32 code (tests/golden/nio3d_fno_train.npz,
-tests/golden/make_golden_nio3d_fno.py), the model's state_dict layout, the C ABI symbols of
+tests/golden/make_golden_nio3d_fno.py), the model's state_dict layout, the host-only queries of
 include/blindno_bag3d.h, and what must be rejected.
 
 Bars, those of tests/test_nio3d_golden.py (an fp32 reference measured against float64): out rel-L2
@@ -10,7 +10,6 @@ and 1.4e-6 (worst gradient) against this restatement.
 import ctypes
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -21,8 +20,6 @@ from recipe import make_array
 
 import nio3d_fno_ref
 
-NEW_SYMBOLS = ["blindno_project_bag3d_fwd", "blindno_project_bag3d_bwd",
-               "blindno_project_bag3d_stats_floats", "blindno_project_bag3d_bwd_nchunk"]
 CSRC = os.path.join(ROOT, "reconstruction-of-pde-without-time-label_amd", "csrc")
 
 
@@ -112,26 +109,12 @@ def test_golden_layout_is_the_model_layout():
     assert sorted("g." + k for k in trained) == sorted(k for k in g if k.startswith("g."))
 
 
-def test_new_symbols_declared_and_bound():
-    """include/blindno_bag3d.h (included by blindno.h) <=> _lib.SIGNATURES_BAG3D <=> the library."""
+def test_bag3d_queries_without_a_device():
+    """Host-only size queries work without a device: 3 KiB of statistics per point, in 16-point
+    tiles."""
     import blindno
     from blindno import _lib
-    assert '#include "blindno_bag3d.h"' in open(os.path.join(ROOT, "include", "blindno.h")).read()
-    hdr = open(os.path.join(ROOT, "include", "blindno_bag3d.h")).read()
-    decl = sorted(set(re.findall(r"^(?:int|int64_t|const char\*)\s+(blindno_\w+)\(", hdr, re.M)))
-    assert decl == sorted(NEW_SYMBOLS) == sorted(_lib.SIGNATURES_BAG3D)
-    others = (set(_lib.SIGNATURES) | set(_lib.SIGNATURES_CONV3D) | set(_lib.SIGNATURES_FPE) |
-              set(_lib.SIGNATURES_GPE2D))
-    assert not set(_lib.SIGNATURES_BAG3D) & others
-    lib = blindno.load_library()
-    for s in NEW_SYMBOLS:
-        assert hasattr(lib, s) and s in _lib.exported_symbols(), s
-        m = re.search(r"\b(?:int|int64_t)\s+" + s + r"\s*\(([^;]*)\)\s*;", hdr)
-        assert m, s
-        nargs = len([a for a in m.group(1).split(",") if a.strip()])
-        assert nargs == len(_lib.SIGNATURES_BAG3D[s]) == len(getattr(lib, s).argtypes), (s, nargs)
-    assert lib.blindno_project_bag3d_stats_floats.restype is ctypes.c_int64
-    # host-only size queries work without a device: 3 KiB of statistics per point, in 16-point tiles
+    assert blindno.load_library().blindno_project_bag3d_stats_floats.restype is ctypes.c_int64
     assert _lib.query("blindno_project_bag3d_stats_floats", 2, 7, 6, 5) == (420 + 15) // 16 * 16 * 768
     assert _lib.query("blindno_project_bag3d_stats_floats", 4, 40, 40, 40) * 4 == 4 * 40 ** 3 * 3072
     assert 1 <= _lib.query("blindno_project_bag3d_bwd_nchunk", 2, 7, 6, 5) <= 27
@@ -145,17 +128,13 @@ def test_no_atomics_in_the_kernel_source():
 
 def _rc(lib, name, dims):
     """The entry called with non-NULL placeholder pointers: only reached when it refuses."""
-    npt = len(blindno_sig(name)) - len(dims) - 1
+    from blindno import _lib
+    npt = len(_lib.signature(name)[0]) - len(dims) - 1
     if name.endswith("_bwd"):                       # ... partial, nchunk, dims
         args = [ctypes.c_void_p(64)] * (npt - 1) + [1] + list(dims)
     else:
         args = [ctypes.c_void_p(64)] * npt + list(dims)
     return getattr(lib, name)(*args, None)
-
-
-def blindno_sig(name):
-    from blindno import _lib
-    return _lib.SIGNATURES_BAG3D[name]
 
 
 @pytest.mark.parametrize("name", ["blindno_project_bag3d_fwd", "blindno_project_bag3d_bwd"])

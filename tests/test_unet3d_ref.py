@@ -134,22 +134,8 @@ def test_layout_matches_fixture_and_module_imports_without_a_gpu():
             m(bad)
 
 
-def test_symbols_declared_and_bound():
-    """include/blindno_unet3d.h (included by blindno.h) <=> _lib.SIGNATURES_UNET3D <=> the library."""
-    import re
-    import blindno
+def test_unet3d_queries_without_a_device():
     from blindno import _lib
-    from conftest import ROOT
-    assert '#include "blindno_unet3d.h"' in open(os.path.join(ROOT, "include", "blindno.h")).read()
-    hdr = open(os.path.join(ROOT, "include", "blindno_unet3d.h")).read()
-    decl = sorted(set(re.findall(r"^int\s+(blindno_\w+)\(", hdr, re.M)))
-    assert decl == sorted(_lib.SIGNATURES_UNET3D) and len(decl) == 10
-    lib = blindno.load_library()
-    for s in decl:
-        assert hasattr(lib, s) and s in _lib.exported_symbols(), s
-        m = re.search(r"\bint\s+" + s + r"\s*\(([^;]*)\)\s*;", hdr)
-        nargs = len([a for a in m.group(1).split(",") if a.strip()])
-        assert nargs == len(_lib.SIGNATURES_UNET3D[s]) == len(getattr(lib, s).argtypes), (s, nargs)
     q = _lib.query
     assert q("blindno_dwconv3d_wgrad_nsplit", 1, 1, 6, 11, 41, 7, 7, 7) == 8      # capped by the 8 work items
     assert q("blindno_dwconv3d_wgrad_nsplit", 400, 1, 40, 40, 40, 7, 7, 7) == 147  # ceil(1024 / 7)
